@@ -24,7 +24,7 @@ Workloads:
                     slices: fp32 activations of every conv would need ~750 GB, so layer1-2 of every MRI encoder (and layer3
                     of the encoder whose backward runs last) are rebuilt in backward from their stage inputs + BatchNorm
                     statistics (`activation_recompute` in the JSON).
-                    The same run also times two secondaries at the reference's native sizes (10 steps each): `native3` (same
+                    With --full the same run also times two secondaries at the reference's native sizes (10 steps each): `native3` (same
                     model, XR 350^2 + DESS 160x160x64 + TSE 160x160x32 + T2 160x160x25) and `native` (XR1MR2C1CnnTrf exactly
                     as runner.sh:341-363, the largest model the reference registers, parity-pinned by reference fixtures).
   native3 / native  those two as the primary workload.
@@ -32,9 +32,13 @@ Workloads:
   xr1cnn / xr1c1    BASELINE configs 1 / 2 (XR1Cnn B=4; extension XR1C1Cnn = XR + clinical MLP head, B=32) @350^2.
   mr1 / mr1c1       BASELINE config 3: MR1CnnTrf B=4 @160x160x64; extension MR1C1CnnTrf (DESS + clinical) B=4 @384x384x160.
   eval3             inference pass of the native3 model (eval() mode, no autograd); `value` = knees/s scored.
-The JSON line carries `roofline` for the dominant kernel (the MFMA GEMM, timed live with events on the launch stream over
-one extra instrumented single-stream step) and `cpu_baseline` (the oracle = CPU port of the same step, timed on this box's
-host cores on a bounded sample).
+A plain run sets up, warms up, times the K steps and prints the JSON line.  With --full the line also carries `roofline` for
+the dominant kernel (the MFMA GEMM, timed live with events on the launch stream over one extra instrumented single-stream
+step), the secondaries of the default workload (see syn3 above) and `cpu_baseline` (the oracle = CPU port of the same step,
+timed on the host's CPU cores on a bounded sample).  --breakdown runs the instrumented step as well.
+--dump-outputs DIR writes what the last timed step computed (loss, logits, a fixed sample of the updated parameters, their
+gradients and the BatchNorm buffers) as .npy files; inputs, weights and dropout streams are seeded, so two builds given the
+same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -81,6 +85,12 @@ def parse_args(argv=None):
     ap.add_argument("--serial", action="store_true",
                     help="one HIP stream only (no encoder lanes / wgrad side stream): kernel durations seen by a profiler "
                          "are then not inflated by co-running kernels -- the mode the roofline step always uses")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented roofline step, the secondaries of the default "
+                         "run and the CPU baseline.  Without it a run sets up, warms up, times the K steps and prints its line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64): "
+                         "loss and logits, and a fixed sample of the updated parameters, their gradients and the BatchNorm buffers")
     return ap.parse_args(argv)
 
 
@@ -265,6 +275,46 @@ def apply_recompute(model, policy):
     for t, e in zip(mri, ents):
         t.recompute = [int(ch) for ch in e]
     return policy
+
+
+DUMP_SAMPLE = 2048       # elements per parameter / gradient / buffer in the --dump-outputs samples
+
+
+def dump_outputs(outdir, model, last):
+    """--dump-outputs: what the last timed step computed, as float32 / float64 .npy files in `outdir`.  `last` holds the step's
+    own results (loss and logits; logits and probabilities for eval3); the updated parameters, their gradients and the
+    BatchNorm buffers are sampled at up to DUMP_SAMPLE logical positions per tensor, drawn from a generator seeded by the
+    tensor's name (the same positions in every run and every build), and concatenated in named_parameters / named_buffers order."""
+    import zlib
+    import numpy as np
+    import torch
+
+    def sample(named):
+        parts = []
+        for name, t in named:
+            n = t.numel()
+            if n == 0:
+                continue
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, n, size=min(n, DUMP_SAMPLE)))
+            pos = tuple(torch.from_numpy(np.ascontiguousarray(i)).to(t.device) for i in np.unravel_index(idx, tuple(t.shape)))
+            parts.append(t.detach()[pos].float())
+        return torch.cat(parts).cpu().numpy() if parts else np.zeros(0, np.float32)
+
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()        # (every stream of the step has landed)
+    out = {k: (v.detach().double().cpu().numpy().reshape(1) if k == "loss" else v.detach().float().cpu().numpy())
+           for k, v in last.items()}
+    if "loss" in last:      # a train step: it also moved the parameters and left their gradients and the running statistics
+        params = list(model.named_parameters())
+        out["params_sample"] = sample(params)
+        out["grads_sample"] = sample((n, p.grad if p.grad is not None else torch.zeros_like(p)) for n, p in params)
+        out["buffers_sample"] = sample((n, b) for n, b in model.named_buffers() if b.dtype.is_floating_point)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+    total = sum(v.nbytes for v in out.values())
+    print(f"bench.py: wrote {len(out)} arrays ({total / 2**20:.1f} MiB) to {outdir}: "
+          + ", ".join(f"{k} {tuple(v.shape)}" for k, v in out.items()), file=sys.stderr)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -467,6 +517,7 @@ def main(args):
 
             def step_eval():
                 logits, proba = predict_batch(model, xs)
+                job_state["last"] = {"logits": logits, "proba": proba}
                 return float(proba[0, 0].item())       # the driver's per-batch host read (argmax / softmax go to the CPU)
             return cfg, B, policy, step_eval
 
@@ -477,7 +528,9 @@ def main(args):
             gstep = GraphedTrainStep(model, lambda lg, tg: loss_fn(input=lg, target=tg), opt, xs, y, warmup=2)
 
             def step_graph():
-                return gstep(xs, y)[1].item()
+                logits, loss = gstep(xs, y)
+                job_state["last"] = {"logits": logits, "loss": loss}
+                return loss.item()
             return cfg, B, policy, step_graph
 
         def step():
@@ -488,6 +541,7 @@ def main(args):
             if dist_on:
                 ddp.reduce_gradients()      # (time_exposed: events around the compute stream's waits on the collectives)
             opt.step()
+            job_state["last"] = {"logits": logits.detach(), "loss": loss.detach()}
             return loss.item()          # (see the module docstring: `host_sync`)
         return cfg, B, policy, step
 
@@ -530,6 +584,8 @@ def main(args):
     cfg, B, policy, step = make_job(args.workload, args.batch, args.recompute)
     torch.cuda.reset_peak_memory_stats()
     dt, lv, per = timed(step, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job_state["model"], job_state["last"])
     per_rank_ms = [round(t / args.steps * 1e3, 2) for t in rank_dt] if rank_dt else None
     hbm_gb = (round(torch.cuda.max_memory_allocated() / 2**30, 1), round(torch.cuda.max_memory_reserved() / 2**30, 1))
     comm_exposed, comm_exposed_ranks = None, None
@@ -550,77 +606,110 @@ def main(args):
                               "config": {"workload": f"{args.workload}: {cfg['name']} train step replayed from a HIP graph "
                                                      f"(run.GraphedTrainStep), per-GPU batch {B}", "last_loss": round(lv, 6)}}))
         return
-    # one extra instrumented step: live event timing of every MFMA-GEMM launch on its launch stream
-    _encoder.USE_SIDE_STREAM = False      # serialise: per-kernel durations are not inflated by co-running kernels
-    _common.USE_LANES = False
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()              # the serial step allocates from another stream pool: start it clean
-    step()                                # (untimed) settle the allocator on the new pool
-    torch.cuda.synchronize()
-    ops.PROFILE = []
-    step()
-    torch.cuda.synchronize()
-    prof = [(f, fl, e0.elapsed_time(e1), tag, nb, mpp) for f, fl, e0, e1, tag, nb, mpp in ops.PROFILE if f == "gemm"]
-    ops.PROFILE = None
-    gemm_ms = sum(p[2] for p in prof)
-    gemm_flop = sum(p[1] for p in prof)
-    gemm_bytes = sum(p[4] for p in prof)
-    n_launch = len(prof)
-    achieved_exec = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    # ALGORITHMIC work of the step (per-sample figure x the samples one step processes) over the measured duration of
-    # the dominant kernel family: recomputed forward stages are time spent, not work done
-    algo_flop = algorithmic_train_gflop_per_sample(args.workload) * 1e9 * B
-    achieved = algo_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
 
-    def call_peak(mpp):
-        return BF16_MFMA_PEAK_TFLOPS / mpp
+    def roofline(value):
+        """one extra instrumented step: live event timing of every MFMA-GEMM launch on its launch stream -> the
+        `roofline` entry of the line (and the --breakdown table)"""
+        _encoder.USE_SIDE_STREAM = False      # serialise: per-kernel durations are not inflated by co-running kernels
+        _common.USE_LANES = False
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()              # the serial step allocates from another stream pool: start it clean
+        step()                                # (untimed) settle the allocator on the new pool
+        torch.cuda.synchronize()
+        ops.PROFILE = []
+        step()
+        torch.cuda.synchronize()
+        prof = [(f, fl, e0.elapsed_time(e1), tag, nb, mpp) for f, fl, e0, e1, tag, nb, mpp in ops.PROFILE if f == "gemm"]
+        ops.PROFILE = None
+        gemm_ms = sum(p[2] for p in prof)
+        gemm_flop = sum(p[1] for p in prof)
+        gemm_bytes = sum(p[4] for p in prof)
+        n_launch = len(prof)
+        achieved_exec = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # ALGORITHMIC work of the step (SURVEY 8(d): per-sample figure x the samples one step processes) over the measured duration of
+        # the dominant kernel family: recomputed forward stages are time spent, not work done
+        algo_flop = algorithmic_train_gflop_per_sample(args.workload) * 1e9 * B
+        achieved = algo_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
 
-    def call_floor_ms(fl, nb, mpp):
-        """roofline time of one call: the larger of its matrix-pipe time and the time to move each operand once"""
-        return max(fl / (call_peak(mpp) * 1e12), nb / (HBM_PEAK_TBPS * 1e12)) * 1e3
-    floor_ms = sum(call_floor_ms(fl, nb, mpp) for f, fl, ms, tag, nb, mpp in prof)
-    hbm_ms = sum(ms for f, fl, ms, tag, nb, mpp in prof if nb / (HBM_PEAK_TBPS * 1e12) > fl / (call_peak(mpp) * 1e12))
-    if args.breakdown and rank == 0:
-        agg = {}
-        for f, fl, ms, tag, nb, mpp in prof:
-            a = agg.setdefault((tag, mpp), [0, 0.0, 0.0, 0.0, 0.0])
-            a[0] += 1; a[1] += fl; a[2] += ms; a[3] += nb; a[4] += call_floor_ms(fl, nb, mpp)
-        with open(args.breakdown, "w") as fh:
-            fh.write(f"# per-shape GEMM-family calls of one train step ({args.workload}, batch {B}, recompute {policy}); ms from events on "
-                     f"the launch stream;\n# mpp = matrix instructions per product (3: fp16 x 2 scheme, 6: bf16 x 3); MB = algorithmic HBM "
-                     f"bytes (every operand once); floor = max(FLOP / (2500 TFLOP/s / mpp), bytes / {HBM_PEAK_TBPS:g} TB/s); bound = which "
-                     f"term of the floor is larger\n")
-            fh.write(f"{'call':48s} {'mpp':>3s} {'n':>4s} {'ms':>9s} {'GFLOP':>10s} {'TFLOP/s':>8s} {'MB':>9s} {'TB/s':>6s} {'floor ms':>9s} {'bound':>5s}\n")
-            for (tag, mpp), (n, fl, ms, nb, flo) in sorted(agg.items(), key=lambda kv: -kv[1][2]):
-                bound = "hbm" if nb / (HBM_PEAK_TBPS * 1e12) > fl / (call_peak(mpp) * 1e12) else "mfma"
-                fh.write(f"{tag:48s} {mpp:3d} {n:4d} {ms:9.3f} {fl / 1e9:10.1f} {fl / ms / 1e9 if ms > 0 else 0:8.1f} {nb / 1e6:9.1f} "
-                         f"{nb / ms / 1e9 if ms > 0 else 0:6.2f} {flo:9.3f} {bound:>5s}\n")
-    bound_s = sum(fl / (call_peak(mpp) * 1e12) for f, fl, ms, tag, nb, mpp in prof)
-    peak_mix = gemm_flop / bound_s / 1e12 if bound_s > 0 else call_peak(3)
-    f16_share = sum(fl for f, fl, ms, tag, nb, mpp in prof if mpp == 3) / gemm_flop if gemm_flop else 0.0
-    # HBM-side bytes per launch of the dominant kernel cannot be counted from inside the process: they come from
-    # the committed PMC summary of this same workload (profiles/README.md has the command and the corrections)
-    traffic, traffic_src, traffic_step = None, None, None
-    for tj in sorted((ROOT / "profiles").glob(f"r*_gemm_traffic_{args.workload}.json"), reverse=True):      # the newest round's
-        try:
-            tjd = json.loads(tj.read_text())
-            if tjd.get("batch") == B:
-                traffic, traffic_src = tjd["bytes_per_launch"], f"profiles/{tj.name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)"
-                traffic_step = {k: tjd[k] for k in ("bytes_per_step", "act_planes_bytes_per_step", "algorithmic_bytes_per_step",
-                                                    "ratio_to_algorithmic", "ratio_to_algorithmic_with_act_planes") if k in tjd}
-                break
-        except (ValueError, KeyError):
-            pass
+        def call_peak(mpp):
+            return BF16_MFMA_PEAK_TFLOPS / mpp
 
-    traffic_vs_ideal = None
-    ideal_b = survey_ideal_bytes_per_sample(args.workload)
-    if traffic_step and ideal_b:
-        moved = traffic_step.get("bytes_per_step", 0) + traffic_step.get("act_planes_bytes_per_step", 0)
-        traffic_vs_ideal = {"ratio": round(moved / (ideal_b * B), 3), "survey_ideal_bytes_per_step": int(ideal_b * B),
-                            "pmc_bytes_per_step": int(moved),
-                            "ideal_is": "SURVEY 8(d): 7 x sum(conv elements) x 4 B per image (every tensor of a perfectly fused step once: "
-                                        "forward in + out, backward dY twice, X, dX, one BatchNorm-recompute read), x the images of the "
-                                        "batch; pmc = GEMM-family launches + plane-image pre-passes of the committed PMC summary"}
+        def call_floor_ms(fl, nb, mpp):
+            """roofline time of one call: the larger of its matrix-pipe time and the time to move each operand once"""
+            return max(fl / (call_peak(mpp) * 1e12), nb / (HBM_PEAK_TBPS * 1e12)) * 1e3
+        floor_ms = sum(call_floor_ms(fl, nb, mpp) for f, fl, ms, tag, nb, mpp in prof)
+        hbm_ms = sum(ms for f, fl, ms, tag, nb, mpp in prof if nb / (HBM_PEAK_TBPS * 1e12) > fl / (call_peak(mpp) * 1e12))
+        if args.breakdown and rank == 0:
+            agg = {}
+            for f, fl, ms, tag, nb, mpp in prof:
+                a = agg.setdefault((tag, mpp), [0, 0.0, 0.0, 0.0, 0.0])
+                a[0] += 1; a[1] += fl; a[2] += ms; a[3] += nb; a[4] += call_floor_ms(fl, nb, mpp)
+            with open(args.breakdown, "w") as fh:
+                fh.write(f"# per-shape GEMM-family calls of one train step ({args.workload}, batch {B}, recompute {policy}); ms from events on "
+                         f"the launch stream;\n# mpp = matrix instructions per product (3: fp16 x 2 scheme, 6: bf16 x 3); MB = algorithmic HBM "
+                         f"bytes (every operand once); floor = max(FLOP / (2500 TFLOP/s / mpp), bytes / {HBM_PEAK_TBPS:g} TB/s); bound = which "
+                         f"term of the floor is larger\n")
+                fh.write(f"{'call':48s} {'mpp':>3s} {'n':>4s} {'ms':>9s} {'GFLOP':>10s} {'TFLOP/s':>8s} {'MB':>9s} {'TB/s':>6s} {'floor ms':>9s} {'bound':>5s}\n")
+                for (tag, mpp), (n, fl, ms, nb, flo) in sorted(agg.items(), key=lambda kv: -kv[1][2]):
+                    bound = "hbm" if nb / (HBM_PEAK_TBPS * 1e12) > fl / (call_peak(mpp) * 1e12) else "mfma"
+                    fh.write(f"{tag:48s} {mpp:3d} {n:4d} {ms:9.3f} {fl / 1e9:10.1f} {fl / ms / 1e9 if ms > 0 else 0:8.1f} {nb / 1e6:9.1f} "
+                             f"{nb / ms / 1e9 if ms > 0 else 0:6.2f} {flo:9.3f} {bound:>5s}\n")
+        bound_s = sum(fl / (call_peak(mpp) * 1e12) for f, fl, ms, tag, nb, mpp in prof)
+        peak_mix = gemm_flop / bound_s / 1e12 if bound_s > 0 else call_peak(3)
+        f16_share = sum(fl for f, fl, ms, tag, nb, mpp in prof if mpp == 3) / gemm_flop if gemm_flop else 0.0
+        # HBM-side bytes per launch of the dominant kernel cannot be counted from inside the process: they come from
+        # the committed PMC summary of this same workload (profiles/README.md has the command and the corrections)
+        traffic, traffic_src, traffic_step = None, None, None
+        for tj in sorted((ROOT / "profiles").glob(f"r*_gemm_traffic_{args.workload}.json"), reverse=True):      # the newest round's
+            try:
+                tjd = json.loads(tj.read_text())
+                if tjd.get("batch") == B:
+                    traffic, traffic_src = tjd["bytes_per_launch"], f"profiles/{tj.name} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE)"
+                    traffic_step = {k: tjd[k] for k in ("bytes_per_step", "act_planes_bytes_per_step", "algorithmic_bytes_per_step",
+                                                        "ratio_to_algorithmic", "ratio_to_algorithmic_with_act_planes") if k in tjd}
+                    break
+            except (ValueError, KeyError):
+                pass
+
+        traffic_vs_ideal = None
+        ideal_b = survey_ideal_bytes_per_sample(args.workload)
+        if traffic_step and ideal_b:
+            moved = traffic_step.get("bytes_per_step", 0) + traffic_step.get("act_planes_bytes_per_step", 0)
+            traffic_vs_ideal = {"ratio": round(moved / (ideal_b * B), 3), "survey_ideal_bytes_per_step": int(ideal_b * B),
+                                "pmc_bytes_per_step": int(moved),
+                                "ideal_is": "SURVEY 8(d): 7 x sum(conv elements) x 4 B per image (every tensor of a perfectly fused step once: "
+                                            "forward in + out, backward dY twice, X, dX, one BatchNorm-recompute read), x the images of the "
+                                            "batch; pmc = GEMM-family launches + plane-image pre-passes of the committed PMC summary"}
+        return {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak_mix, 1),
+                "unit": "TFLOP/s", "frac": round(achieved / peak_mix, 4),
+                "achieved_executed": round(achieved_exec, 2), "frac_executed": round(achieved_exec / peak_mix, 4),
+                "traffic": traffic,
+                "traffic_unit": "bytes per GEMM-family kernel launch (average)", "traffic_source": traffic_src,
+                "traffic_per_step": traffic_step,
+                "kernel": "koaf_gemm_kernel + wgrad3x3_ring_kernel (implicit GEMM: conv fwd/dgrad/wgrad, linear, attention; fp32 in/out/accumulate; "
+                          "products on v_mfma_f32_32x32x16_f16 from two scaled fp16 pieces per operand (3 MFMAs per product: "
+                          "convolutions) or on v_mfma_f32_32x32x16_bf16 from three bf16 pieces (6 MFMAs: linear, attention, "
+                          "grouped conv))",
+                "peak_is": "2.5 PFLOP/s dense 16-bit MFMA / MFMAs per product, FLOP-weighted harmonic mean over the step's calls "
+                           f"({100 * f16_share:.0f} % of the executed FLOPs on the 3-MFMA scheme at 833.3, the rest at 416.7 TFLOP/s "
+                           "fp32-equivalent)",
+                "achieved_is": "ALGORITHMIC FLOPs of the step (SURVEY 8(d): step_gflop_per_sample_survey x the per-GPU batch) / the "
+                               "event-timed durations of the step's GEMM-family calls on the launch stream (one instrumented "
+                               "single-stream step); achieved_executed / frac_executed count what the calls execute instead "
+                               "(recomputed forward stages included)",
+                "fp32_mfma_peak": MFMA_F32_PEAK_TFLOPS,
+                "achieved_over_fp32_mfma_peak": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),
+                "traffic_vs_survey_ideal": traffic_vs_ideal,
+                "floor_ms_per_step": round(floor_ms, 2), "frac_of_floor": round(floor_ms / gemm_ms, 4) if gemm_ms > 0 else None,
+                "hbm_bound_share_of_kernel_ms": round(hbm_ms / gemm_ms, 4) if gemm_ms > 0 else None,
+                "floor_is": "sum over the step's calls of max(FLOP / matrix-pipe bound of the call, algorithmic bytes / 8 TB/s): "
+                            "SURVEY 8(d)'s attainable = min(MFMA peak, AI x HBM) applied per call; frac_of_floor = floor / "
+                            "measured kernel time; `frac` above stays the plain achieved / matrix-pipe peak",
+                "launches_per_step": n_launch, "kernel_ms_per_step": round(gemm_ms, 2),
+                "executed_gflop_per_step": round(gemm_flop / 1e9, 1),
+                "algorithmic_gbytes_per_step": round(gemm_bytes / 1e9, 1),
+                "step_gflop_per_sample_survey": algorithmic_train_gflop_per_sample(args.workload),
+                "step_tflops_algorithmic": round(algorithmic_train_gflop_per_sample(args.workload) * value / 1e3 / world, 1)}
 
     def one_step_outputs(perturb=False):
         """eval logits, train logits / loss and the flat gradient arena of ONE forward + backward of the current job's model on
@@ -707,8 +796,11 @@ def main(args):
         free()
         return res
 
+    value = world * B * args.steps / dt
+    roof = roofline(value) if (args.full or args.breakdown) else None
+
     secondary = {}
-    if (args.workload == "syn3" and not args.batch and args.recompute == "auto" and not args.no_secondary
+    if (args.full and args.workload == "syn3" and not args.batch and args.recompute == "auto" and not args.no_secondary
             and args.steps >= 10):
         _common.USE_LANES, _encoder.USE_SIDE_STREAM = (False, False) if args.serial else lanes_default
         try:
@@ -790,7 +882,6 @@ def main(args):
                 secondary[name] = {"error": f"{type(e).__name__}: {e}"[:300]}
 
     if rank == 0:
-        value = world * B * args.steps / dt
         out = {
             "metric": ("knees/sec full XR+MRI+clin fusion inference pass" if args.workload == "eval3"
                        else "knees/sec full XR+MRI+clin fusion train step"),
@@ -815,41 +906,13 @@ def main(args):
                        "hbm_peak_gib": {"allocated": hbm_gb[0], "reserved": hbm_gb[1]}},
             "rccl_ranks": rccl_ranks, "comm_exposed_ms": comm_exposed,
             "per_rank": {"ms_per_step": per_rank_ms, "comm_exposed_ms": comm_exposed_ranks} if dist_on else None,
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": round(peak_mix, 1),
-                         "unit": "TFLOP/s", "frac": round(achieved / peak_mix, 4),
-                         "achieved_executed": round(achieved_exec, 2), "frac_executed": round(achieved_exec / peak_mix, 4),
-                         "traffic": traffic,
-                         "traffic_unit": "bytes per GEMM-family kernel launch (average)", "traffic_source": traffic_src,
-                         "traffic_per_step": traffic_step,
-                         "kernel": "koaf_gemm_kernel + wgrad3x3_ring_kernel (implicit GEMM: conv fwd/dgrad/wgrad, linear, attention; fp32 in/out/accumulate; "
-                                   "products on v_mfma_f32_32x32x16_f16 from two scaled fp16 pieces per operand (3 MFMAs per product: "
-                                   "convolutions) or on v_mfma_f32_32x32x16_bf16 from three bf16 pieces (6 MFMAs: linear, attention, "
-                                   "grouped conv))",
-                         "peak_is": "2.5 PFLOP/s dense 16-bit MFMA / MFMAs per product, FLOP-weighted harmonic mean over the step's calls "
-                                    f"({100 * f16_share:.0f} % of the executed FLOPs on the 3-MFMA scheme at 833.3, the rest at 416.7 TFLOP/s "
-                                    "fp32-equivalent)",
-                         "achieved_is": "ALGORITHMIC FLOPs of the step (SURVEY 8(d): step_gflop_per_sample_survey x the per-GPU batch) / the "
-                                        "event-timed durations of the step's GEMM-family calls on the launch stream (one instrumented "
-                                        "single-stream step); achieved_executed / frac_executed count what the calls execute instead "
-                                        "(recomputed forward stages included)",
-                         "fp32_mfma_peak": MFMA_F32_PEAK_TFLOPS,
-                         "achieved_over_fp32_mfma_peak": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),
-                         "traffic_vs_survey_ideal": traffic_vs_ideal,
-                         "floor_ms_per_step": round(floor_ms, 2), "frac_of_floor": round(floor_ms / gemm_ms, 4) if gemm_ms > 0 else None,
-                         "hbm_bound_share_of_kernel_ms": round(hbm_ms / gemm_ms, 4) if gemm_ms > 0 else None,
-                         "floor_is": "sum over the step's calls of max(FLOP / matrix-pipe bound of the call, algorithmic bytes / 8 TB/s): "
-                                     "SURVEY 8(d)'s attainable = min(MFMA peak, AI x HBM) applied per call; frac_of_floor = floor / "
-                                     "measured kernel time; `frac` above stays the plain achieved / matrix-pipe peak",
-                         "launches_per_step": n_launch, "kernel_ms_per_step": round(gemm_ms, 2),
-                         "executed_gflop_per_step": round(gemm_flop / 1e9, 1),
-                         "algorithmic_gbytes_per_step": round(gemm_bytes / 1e9, 1),
-                         "step_gflop_per_sample_survey": algorithmic_train_gflop_per_sample(args.workload),
-                         "step_tflops_algorithmic": round(algorithmic_train_gflop_per_sample(args.workload) * value / 1e3 / world, 1)},
         }
+        if roof is not None:
+            out["roofline"] = roof
         out["numerics"] = ops.numerics_status()       # clamped activations / non-finite operand scales over the whole run: must be 0 / 0
         if secondary:
             out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload)
             if cb is not None:
                 out["cpu_baseline"] = cb

@@ -473,6 +473,24 @@ def interpolate(x, scale_factor):
     return F.interpolate(x, scale_factor=scale_factor, recompute_scale_factor=True, align_corners=False, mode=mode)
 
 
+def _affine_grid_2d(mat, size):
+    """F.affine_grid(mat[None].repeat(N, 1, 1), size, align_corners=False) for a float32 (2, 3) `mat`, with its rounding
+    pinned: per point, x * m[:, 0] rounded, y * m[:, 1] fused onto it with ONE rounding, then + m[:, 2] -- the float32
+    batched matmul inside F.affine_grid on the host the F12 vectors were recorded on (bit for bit there).  F.affine_grid's
+    own rounding follows the host's BLAS, and one unit in the last place of a sampling coordinate moves a normalised
+    bilinear sample by up to ~6e-6: the grid must not depend on the host.  (Products of two float32 values are exact in
+    float64, so the fused step is exact before its one rounding to float32.)"""
+    ident = torch.tensor([[[1., 0., 0.], [0., 1., 0.]]]).repeat(size[0], 1, 1)
+    base = F.affine_grid(ident, size, align_corners=False)                  # (x, y) of every output pixel, exact
+    bx, by = base[..., 0], base[..., 1]
+    cols = []
+    for r in range(2):
+        t = bx * mat[r, 0]
+        t = (by.double() * mat[r, 1].double() + t.double()).float()
+        cols.append(t + mat[r, 2])
+    return torch.stack(cols, dim=-1)
+
+
 def augment_sample(x, state, mean, std, rotate_prob=0.5, gamma_prob=0.5):
     """One sample through the reference's train-time tensor pipeline of an image modality
     (koafusion/datasets/_data_provider.py:295-335): PTToUnitRange (_pt.py:75-99) -> PTRotate2D / PTRotate3DInSlice
@@ -487,7 +505,7 @@ def augment_sample(x, state, mean, std, rotate_prob=0.5, gamma_prob=0.5):
         th = torch.tensor(float(theta))
         mat = torch.tensor([[torch.cos(th), -torch.sin(th), 0], [torch.sin(th), torch.cos(th), 0]])
         img = x.permute(3, 0, 1, 2) if x.dim() == 4 else x[None]              # (slices | 1, CH, R, C)
-        grid = F.affine_grid(mat[None].to(img.dtype).repeat(img.shape[0], 1, 1), img.size(), align_corners=False)
+        grid = _affine_grid_2d(mat.to(img.dtype), img.size())
         img = F.grid_sample(img, grid.to(img.dtype), align_corners=False)
         x = img.permute(1, 2, 3, 0) if x.dim() == 4 else img[0]
     if p_gam < gamma_prob:

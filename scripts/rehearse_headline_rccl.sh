@@ -6,6 +6,6 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-KOAF_DIST_REHEARSAL=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 --no-secondary --no-cpu-baseline > $OUT/rccl_rehearsal_syn3.log 2> $OUT/rccl_rehearsal_syn3.err || exit 1
+KOAF_DIST_REHEARSAL=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29544 timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 --full --no-secondary --no-cpu-baseline > $OUT/rccl_rehearsal_syn3.log 2> $OUT/rccl_rehearsal_syn3.err || exit 1
 timeout -k 10 200 python3 scripts/host_time.py native3 > $OUT/host_time_native3.log 2>&1 || exit 2
 timeout -k 10 300 python3 scripts/host_time.py syn3 > $OUT/host_time_syn3.log 2>&1 || exit 3

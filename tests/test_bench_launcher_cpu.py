@@ -117,3 +117,37 @@ def test_one_gpu_runs_under_the_gpu_free_supervisor_too(tmp_path, capfd):
     assert rc == 0 and json.loads(cap.out.strip().splitlines()[-1])["argv"] == ["--recompute", bench.FALLBACK_POLICY]
     src = (ROOT / "bench.py").read_text()
     assert 'if "WORLD_SIZE" not in os.environ and not _args.inproc:' in src
+
+
+def test_plain_run_is_lean_unless_full():
+    """a plain run times the headline only: the roofline step, secondaries and CPU baseline sit behind --full"""
+    import bench
+    a = bench.parse_args([])
+    assert not a.full and a.dump_outputs == ""
+    a = bench.parse_args(["--full", "--dump-outputs", "d", "--steps", "3"])
+    assert a.full and a.dump_outputs == "d" and a.steps == 3
+
+
+def test_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: float32 / float64 arrays, the same sample positions on every call, far below the 64 MB bound"""
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(300, 5000), torch.nn.BatchNorm1d(5000), torch.nn.Linear(5000, 2))
+    for p in m.parameters():
+        p.grad = torch.randn_like(p)
+    last = {"logits": torch.randn(4, 1, 2), "loss": torch.tensor(0.25)}
+    bench.dump_outputs(str(tmp_path / "a"), m, last)
+    bench.dump_outputs(str(tmp_path / "b"), m, last)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["buffers_sample.npy", "grads_sample.npy", "logits.npy", "loss.npy", "params_sample.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+        total += x.nbytes
+    assert total < 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [0.25]
+    w = m[0].weight.detach().reshape(-1).numpy()
+    assert np.isin(np.load(tmp_path / "a" / "params_sample.npy")[:bench.DUMP_SAMPLE], w).all()
