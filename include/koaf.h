@@ -26,7 +26,7 @@ extern "C" {
 #define KOAF_EINVAL (-1)
 #define KOAF_ELAUNCH (-2)
 
-int koaf_version(void);          /* 100 * major + 10 * minor: 180 = this header */
+int koaf_version(void);          /* 100 * major + 10 * minor: 190 = this header */
 const char* koaf_last_error(void);
 /* Numerics status words: a device uint32[4] (zeroed by the caller; NULL = off, the default) that kernels bump with atomics when
  *   [0] an activation operand left the fp16 range of the fixed activation scale and was CLAMPED (KOAF_ACT_SCALE: |x| > 4094), or
@@ -185,6 +185,25 @@ int koaf_gemm_pick_tile(const KoafGemm* g, int32_t* bm, int32_t* bn);
 /* number of per-tile partial rows (stats / bnb_part) koaf_gemm writes for this descriptor (mixed-height tiling
  * included); callers size / slice their buffers with it */
 int koaf_gemm_part_rows(const KoafGemm* g);
+/* Launch record (tests; off by default): which kernel variant served each koaf_gemm call.  While switched on, every koaf_gemm
+ * launch appends one entry -- plain host memory, written before the launch; no device work, nothing when off.  `variant` is the
+ * tag koaf_gemm reports launch errors under ("koaf_gemm", "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"); `tiles` the
+ * block tiles of one (split, batch) slice and `grid_x` the blocks launched for them (grid_x < tiles: persistent blocks that walk
+ * several tiles).  A convolution entry point that issues several GEMMs (a stride-2 data gradient: one per phase) leaves one
+ * entry per GEMM.  koaf_launch_log(on) clears the record, switches it on / off and returns the previous setting;
+ * koaf_launch_log_read copies the first `cap` entries to `out` (NULL with cap 0: count only) and returns how many launches were
+ * seen since the record was cleared (the record itself keeps the first 4096).  Process-wide, guarded by a mutex. */
+typedef struct KoafLaunchRec {
+    char variant[24];
+    int32_t bm, bn;           /* block tile (halo kernels: 128 | 256 rows) */
+    int32_t tiles, grid_x;
+    int32_t splitk, nbatch;   /* grid.y, grid.z */
+    int32_t fmt, a_tf, b_tf, act16;
+    int32_t M, N, K;
+    int32_t emit;             /* KoafGemm.out_planes != NULL */
+} KoafLaunchRec;
+int koaf_launch_log(int on);
+int koaf_launch_log_read(KoafLaunchRec* out, int32_t cap);
 /* out[i] = sum_s slabs[s][i], i < n, n % 4 == 0 (deterministic split-K combine).  The slab workspace must
  * hold (nslab + 16) * n floats: large counts are folded in two levels through the 16 trailing slabs. */
 int koaf_slab_reduce(const float* slabs, int32_t nslab, int64_t n, float* out, void* stream);

@@ -161,6 +161,26 @@ class KoafBnApply(ctypes.Structure):
     _fields_ = [("dz", ctypes.c_void_p), ("c", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("amax", ctypes.c_void_p)]
 
 
+class KoafLaunchRec(ctypes.Structure):
+    _fields_ = [
+        ("variant", ctypes.c_char * 24),
+        ("bm", ctypes.c_int32),
+        ("bn", ctypes.c_int32),
+        ("tiles", ctypes.c_int32),
+        ("grid_x", ctypes.c_int32),
+        ("splitk", ctypes.c_int32),
+        ("nbatch", ctypes.c_int32),
+        ("fmt", ctypes.c_int32),
+        ("a_tf", ctypes.c_int32),
+        ("b_tf", ctypes.c_int32),
+        ("act16", ctypes.c_int32),
+        ("M", ctypes.c_int32),
+        ("N", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("emit", ctypes.c_int32),
+    ]
+
+
 _SCALARS = {
     "int": ctypes.c_int,
     "int32_t": ctypes.c_int32,
@@ -188,6 +208,8 @@ def _ctype(decl: str):
             return ctypes.POINTER(KoafTail)
         if base == "KoafEmit":
             return ctypes.POINTER(KoafEmit)
+        if base == "KoafLaunchRec":
+            return ctypes.POINTER(KoafLaunchRec)
         if base == "char":
             return ctypes.c_char_p
         return ctypes.c_void_p

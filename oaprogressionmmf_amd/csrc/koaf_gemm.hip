@@ -39,7 +39,11 @@
 //       Double-buffered: the DMA of k-tile t+1 lands while tile t is multiplied.
 #include "koaf_common.h"
 #include <stdlib.h>
+#include <string.h>
+#include <atomic>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 // In-kernel phase stamps (diagnostic builds only: make STAMPS=1 -> libkoaf_stamps.so, scripts/stamps_*.py): thread 0 of every
 // block adds the 100 MHz real-time counter differences between its phase boundaries to a device table.
@@ -2392,25 +2396,53 @@ int operand_mode(const KoafOperand& o) {
     return o.gather == 0 ? M_KM : (o.gather == 1 ? M_KM_G1 : M_KM_G3);
 }
 
+// the launch record (koaf.h koaf_launch_log): host memory only, written before the launch; one relaxed load when switched off
+std::atomic<int> g_log_on{0};
+std::mutex g_log_mutex;
+std::vector<KoafLaunchRec> g_log;
+int64_t g_log_seen = 0;
+constexpr size_t LOG_CAP = 4096;
+
+void log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched) {
+    if (!g_log_on.load(std::memory_order_relaxed)) return;
+    KoafLaunchRec r;
+    memset(&r, 0, sizeof(r));
+    strncpy(r.variant, variant, sizeof(r.variant) - 1);
+    r.bm = g.bm; r.bn = g.bn;
+    r.tiles = (int32_t)grid.x; r.grid_x = (int32_t)launched.x;
+    r.splitk = (int32_t)launched.y; r.nbatch = (int32_t)launched.z;
+    r.fmt = g.fmt; r.a_tf = g.A.tf; r.b_tf = g.B.tf; r.act16 = g.act16;
+    r.M = g.M - g.m_base; r.N = g.N; r.K = g.K;
+    r.emit = g.out_planes != nullptr;
+    std::lock_guard<std::mutex> lock(g_log_mutex);
+    ++g_log_seen;
+    if (g_log.size() < LOG_CAP) g_log.push_back(r);
+}
+
 #define KOAF_LAUNCH(AMODE, BMODE, TA, TB)                                                                        \
+    log_launch("koaf_gemm", g, grid, grid);                                                                      \
     hipLaunchKernelGGL((koaf_gemm_kernel<BM, BN, AMODE, BMODE, TA, TB, VEC, F16, 256, ACT>), grid, dim3(256), 0, s, g);      \
     return koaf_check_launch("koaf_gemm")
 // the persistent variants (fp32 A loader + weight tiles by DMA): at most two blocks per CU, each walking its tiles
 #define KOAF_LAUNCH_P(AMODE, BMODE, TA, TB)                                                                      \
+    log_launch("koaf_gemm", g, grid, persist_mode(AMODE, BMODE, F16, TA) ? pgrid : grid);                        \
     hipLaunchKernelGGL((koaf_gemm_kernel<BM, BN, AMODE, BMODE, TA, TB, VEC, F16, 256, ACT>), (persist_mode(AMODE, BMODE, F16, TA) ? pgrid : grid), dim3(256), 0, s, g);     \
     return koaf_check_launch("koaf_gemm")
 
 // KoafGemm.out_planes (the epilogue also cuts the consumer's plane images): the instantiations with EMIT, for the calls that use it
 // -- dense 1x1 forward convolutions with weight plane images (plain, BatchNorm-prologue and bottleneck-tail loaders)
 #define KOAF_LAUNCH_E(AMODE, BMODE, TA, TB)                                                                      \
+    log_launch("koaf_gemm/emit", g, grid, grid);                                                                 \
     hipLaunchKernelGGL((koaf_gemm_kernel<BM, BN, AMODE, BMODE, TA, TB, VEC, F16, 256, ACT, true>), grid, dim3(256), 0, s, g);      \
     return koaf_check_launch("koaf_gemm/emit")
 #define KOAF_LAUNCH_PE(AMODE, BMODE, TA, TB)                                                                     \
+    log_launch("koaf_gemm/emit", g, grid, persist_mode(AMODE, BMODE, F16, TA) ? pgrid : grid);                   \
     hipLaunchKernelGGL((koaf_gemm_kernel<BM, BN, AMODE, BMODE, TA, TB, VEC, F16, 256, ACT, true>), (persist_mode(AMODE, BMODE, F16, TA) ? pgrid : grid), dim3(256), 0, s, g);     \
     return koaf_check_launch("koaf_gemm/emit")
 
 // the streamed dense A operand (M_KS, StreamA) in front of weight plane images: SD = 2 k-tiles in flight per wave
 #define KOAF_LAUNCH_S(TA, EM)                                                                                    \
+    log_launch("koaf_gemm/stream", g, grid, (TA) < 2 ? pgrid : grid);                                            \
     hipLaunchKernelGGL((koaf_gemm_kernel<BM, BN, M_KS, M_PS, TA, 0, VEC, F16, 256, ACT, EM, 2>), ((TA) < 2 ? pgrid : grid), dim3(256), 0, s, g);      \
     return koaf_check_launch("koaf_gemm/stream")
 // (SD = 4 -- four k-tiles in flight, one tile per block, for the one-source loaders with K >= 256 -- builds without spills (213
@@ -2599,6 +2631,7 @@ int launch_act(const KoafGemm& g, const TilePlan& tp, dim3 grid, hipStream_t s) 
     if (tp.t2d) {
         if constexpr (ACT == 3) { koaf_set_error("koaf_gemm: 2-D tile kernel with act16 = 3"); return KOAF_EINVAL; }
         else {
+            log_launch("koaf_gemm/t2d", g, grid, grid);
             hipLaunchKernelGGL((koaf_gemm_kernel<128, 64, M_PT, M_PS, 0, 0, true, true, 256, ACT>), grid, dim3(256), 0, s, g);
             return koaf_check_launch("koaf_gemm/t2d");
         }
@@ -2627,6 +2660,7 @@ int launch_act(const KoafGemm& g, const TilePlan& tp, dim3 grid, hipStream_t s) 
         // gradient: the BatchNorm-backward operands)
         if constexpr (ACT == 3) { koaf_set_error("koaf_gemm: halo kernel with act16 = 3"); return KOAF_EINVAL; }
         else {
+            log_launch(tp.bm == 128 ? "koaf_gemm/halo128" : "koaf_gemm/halo", g, grid, grid);
             if (tp.bm == 128) {
                 if (tp.bn == 128) hipLaunchKernelGGL((koaf_gemm_kernel<128, 128, M_PH, M_PS, 0, 0, true, true, 256, ACT>), grid, dim3(256), 0, s, g);
                 else hipLaunchKernelGGL((koaf_gemm_kernel<128, 64, M_PH, M_PS, 0, 0, true, true, 256, ACT>), grid, dim3(256), 0, s, g);
@@ -3158,6 +3192,21 @@ extern "C" int koaf_set_stream(int on) {
     const int was = g_stream_mode;
     g_stream_mode = on ? 1 : 0;
     return was;
+}
+
+extern "C" int koaf_launch_log(int on) {
+    std::lock_guard<std::mutex> lock(g_log_mutex);
+    const int was = g_log_on.load(std::memory_order_relaxed);
+    g_log.clear();
+    g_log_seen = 0;
+    g_log_on.store(on ? 1 : 0, std::memory_order_relaxed);
+    return was;
+}
+
+extern "C" int koaf_launch_log_read(KoafLaunchRec* out, int32_t cap) {
+    std::lock_guard<std::mutex> lock(g_log_mutex);
+    for (size_t i = 0; out && i < g_log.size() && (int64_t)i < cap; ++i) out[i] = g_log[i];
+    return (int)(g_log_seen < INT32_MAX ? g_log_seen : INT32_MAX);
 }
 
 extern "C" int koaf_set_conv3x3_halo(int on) {

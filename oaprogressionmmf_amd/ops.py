@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._lib import KoafBnApply, KoafBnb, KoafEmit, KoafGemm, KoafError, KoafTail, KoafWImg, check, lib
+from ._lib import KoafBnApply, KoafBnb, KoafEmit, KoafGemm, KoafError, KoafLaunchRec, KoafTail, KoafWImg, check, lib
 
 _i32 = ctypes.c_int32
 
@@ -200,6 +200,23 @@ def set_stream(on):
     """the streamed kernel for dense 1x1 / stride-1 convolutions and their data gradients (koaf.h koaf_set_stream): True (default) /
     False = the block-wide loader; returns the previous setting"""
     return bool(lib().koaf_set_stream(1 if on else 0))
+
+
+def launch_log(on):
+    """the host-side record of koaf_gemm launches (koaf.h koaf_launch_log; tests): clears it and switches it on / off; returns the
+    previous setting"""
+    return bool(lib().koaf_launch_log(1 if on else 0))
+
+
+def launch_log_read():
+    """the launches recorded since launch_log(True): one dict per koaf_gemm launch, in launch order -- variant ("koaf_gemm",
+    "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"), bm, bn, tiles, grid_x (< tiles: persistent blocks walk), splitk,
+    nbatch, fmt, a_tf, b_tf, act16, M, N, K, emit"""
+    L = lib()
+    n = min(L.koaf_launch_log_read(None, 0), 4096)        # (launches seen; the record keeps the first 4096)
+    buf = (KoafLaunchRec * max(n, 1))()
+    L.koaf_launch_log_read(buf, n)
+    return [{f: (getattr(r, f).decode() if f == "variant" else getattr(r, f)) for f, _ in KoafLaunchRec._fields_} for r in buf[:n]]
 
 
 def use_aplanes(wimg, KH, KW, C):

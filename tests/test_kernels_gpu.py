@@ -1017,16 +1017,30 @@ def _bn_record(ops, dev, x, rows, C):
                            torch.ones(C, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), 0.1, 1e-5, True)
 
 
-@pytest.mark.parametrize("N,H,W,Cin,Cout", [(5, 24, 24, 64, 256),       # K = 64: as many k-steps as tiles in flight, several column tiles
-                                            (600, 12, 12, 64, 128),     # ... and more tiles than resident blocks: the A stream crosses tile boundaries
-                                            (3, 17, 19, 128, 64),       # ragged last tile, 64-column tiles
-                                            (2, 16, 16, 256, 512),      # eight k-steps: four k-tiles in flight (one tile per block)
-                                            (2, 10, 10, 1024, 256)])
-def test_streamed_1x1_kernels_match_the_block_wide_loader(dev, N, H, W, Cin, Cout):
+# The streamed kernel only exists for 128-row tiles, and koaf_gemm_pick_tile shrinks a 128 tile while the grid is under 384 blocks: the
+# small shapes run 64 x 64 tiles, where the switch is never consulted (both runs are the block-wide loader; kept as the 64-row
+# regression they always were).  Each intent has a shape with enough rows to stream; forward and data gradient have the same GEMM
+# dimensions here (rows x Cout, K = Cin: the gradient is that of a Cout -> Cin convolution), so one row count serves both.
+STREAM_CASES = [
+    (5, 24, 24, 64, 256, False),        # 180 tiles of 64 x 64: block-wide on both sides
+    (43, 24, 24, 64, 256, True),        # K = 64: as many k-steps as tiles in flight, two column tiles (388 tiles 128 x 128)
+    (600, 12, 12, 64, 128, True),       # ... and more tiles (675) than resident blocks: the A stream crosses tile boundaries
+    (3, 17, 19, 128, 64, False),        # 16 tiles of 64 x 64, ragged last tile: block-wide on both sides
+    (152, 17, 19, 128, 64, True),       # ragged last tile (72 of 128 rows, 8 of a wave's 32), 64-column tiles (384 tiles 128 x 64)
+    (2, 16, 16, 256, 512, False),       # 64 tiles of 64 x 64: block-wide on both sides
+    (48, 16, 16, 256, 512, True),       # eight k-steps, four column tiles (384 tiles 128 x 128)
+    (2, 10, 10, 1024, 256, False),      # 16 tiles of 64 x 64: block-wide on both sides
+    (245, 10, 10, 1024, 256, True)]     # K = 1024 = the longest k range of the BatchNorm-prologue table (384 tiles, last one ragged)
+
+
+@pytest.mark.parametrize("N,H,W,Cin,Cout,streams", STREAM_CASES, ids=["-".join(str(v) for v in c[:5]) for c in STREAM_CASES])
+def test_streamed_1x1_kernels_match_the_block_wide_loader(dev, N, H, W, Cin, Cout, streams):
     """koaf_set_stream: the streamed kernel of the dense 1x1 / stride-1 convolutions (every wave loads, transforms and splits its own
     32 rows, k-tiles ahead in registers; KoafGemm A mode M_KS) against the block-wide loader on the same calls: outputs, side-stored
     tails, emitted plane images, per-tile BatchNorm statistics, data gradients with the BatchNorm-backward apply on load and the fused
     reduction -- BIT FOR BIT (same pieces, same MFMA order per accumulator, the statistics as the same tree of 32-row band sums).
+    The launch record (koaf_launch_log) says which kernel served each call: with the switch on every forward and gradient call of a
+    `streams` shape ran koaf_gemm/stream on 128-row tiles, with it off none did.
     _torchvision.py:118-138 (the 1x1 convolutions of a Bottleneck)."""
     from oaprogressionmmf_amd import ops
     rows = N * H * W
@@ -1074,11 +1088,24 @@ def test_streamed_1x1_kernels_match_the_block_wide_loader(dev, N, H, W, Cin, Cou
 
     was = ops.set_stream(False)
     try:
+        ops.launch_log(True)
         f0, g0 = forward_calls(), gradient_calls()
+        rec0 = ops.launch_log_read()
         ops.set_stream(True)
+        ops.launch_log(True)
         f1, g1 = forward_calls(), gradient_calls()
+        rec1 = ops.launch_log_read()
     finally:
+        ops.launch_log(False)
         ops.set_stream(was)
+    assert len(rec0) == len(rec1) == len(f0) + len(g0)                   # one GEMM per call, forward and gradient
+    assert all(r["variant"] in ("koaf_gemm", "koaf_gemm/emit") for r in rec0), rec0
+    if streams:
+        assert all(r["variant"] == "koaf_gemm/stream" and r["bm"] == 128 for r in rec1), rec1
+        assert all(r["bm"] == 128 for r in rec0), rec0                   # ... against the block-wide loader on the same tile
+    else:
+        assert all(r["variant"] in ("koaf_gemm", "koaf_gemm/emit") and r["bm"] == 64 for r in rec1), rec1
+    assert [(r["M"], r["N"], r["K"]) for r in rec1] == [(rows, Cout, Cin)] * len(rec1)
     for name in f0:
         a, b = f0[name], f1[name]
         assert torch.equal(a[0], b[0]), name                             # the convolution output
