@@ -30,6 +30,7 @@ static inline int koaf_check_launch(const char* what) {
 }
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -45,7 +46,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // |x| as an unsigned integer: orders like the magnitude for finite values, +Inf above every finite value and every NaN above
 // +Inf -- an integer maximum over these bits PROPAGATES non-finite values, which fmaxf (IEEE maxNum: a NaN operand is dropped)
 // does not.  All "largest magnitude of a tensor" reductions run on these bits, so a NaN / Inf anywhere in an operand reaches
-// its amax scalar, and the GEMM that scales by that amax turns its whole output into NaN (koaf_gemm.hip) instead of clamping
+// its amax scalar, and the GEMM that scales by that amax turns its whole output into NaN (koaf_gemm_kernel.h) instead of clamping
 // the value away.
 __device__ __forceinline__ unsigned koaf_absbits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
 __device__ __forceinline__ bool koaf_bits_finite(unsigned absbits) { return absbits < 0x7f800000u; }

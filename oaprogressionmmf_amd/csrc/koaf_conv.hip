@@ -890,7 +890,7 @@ extern "C" int koaf_linear_wgrad(const float* dy, const float* x, float* dw, flo
 // over (b, head) with strided operands straight out of the fused qkv buffer)
 // ================================================================================================
 int koaf_attention_fwd_fused(const float* qkv, float* attn, float* out, int32_t B, int32_t n, int32_t h, int32_t d, float scale,
-                             void* stream);       // koaf_gemm.hip: ONE launch for n <= 512
+                             void* stream);       // koaf_attention.hip: ONE launch for n <= 512
 
 extern "C" int koaf_attention_fwd(const float* qkv, float* attn, float* out, int32_t B, int32_t n, int32_t h,
                                   int32_t d, float scale, void* stream) {

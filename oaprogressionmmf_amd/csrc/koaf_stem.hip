@@ -25,7 +25,7 @@ constexpr int SM_BAND = 192;                   // output columns per band (six 3
 constexpr int SM_PH = 2 * SM_TH + 5;           // 13 input rows
 constexpr int SM_PW = 2 * SM_BAND + 8;         // 392 input columns (taps 2 ox + 0..7)
 
-// three bf16 pieces of x by truncation (koaf_gemm.hip split3v): x = p0 + p1 + p2 to 2^-24 relative
+// three bf16 pieces of x by truncation (the scalar form of koaf_pieces.h split3v): x = p0 + p1 + p2 to 2^-24 relative
 __device__ __forceinline__ void split3(float x, unsigned& p0, unsigned& p1, unsigned& p2) {
     const unsigned b0 = __float_as_uint(x) & 0xffff0000u;
     const float r1 = x - __uint_as_float(b0);

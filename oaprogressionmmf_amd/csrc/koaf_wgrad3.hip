@@ -1,7 +1,7 @@
 // Weight gradient of the 3x3 / stride-1 / pad-1 convolution over activation plane images (reference: the autograd of
 // F.conv2d in koafusion/models/_torchvision.py:103-136's conv2), k = pixel:
 //     dW[co][kh][kw][ci] = sum_p dy[p][co] * x[p + (kh-1, kw-1)][ci]
-// The generic K-major GEMM (koaf_gemm.hip, M_PK x M_PKG) fetches every x pixel nine times (once per tap) and every dy pixel
+// The generic K-major GEMM (koaf_gemm_aplanes.hip, M_PK x M_PKG) fetches every x pixel nine times (once per tap) and every dy pixel
 // once per column tile through L2 -> LDS, and that path, not the matrix pipe, set its time (64 -> 64 at 96 x 96: 42 GB of LDS-DMA
 // per call, 6.6 ms).  Here both tensors are walked ONCE per (co tile, ci tile) in PADDED raster order -- every image as
 // (H + 2) x (W + 2) positions whose border holds zeros -- so that tap (kh, kw) of position P is simply position
@@ -13,15 +13,9 @@
 #include <stdint.h>
 #include <cstdlib>
 #include "koaf.h"
-#include "koaf_common.h"
+#include "koaf_pieces.h"
 
 namespace {
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-
 struct Wg3Params {
     const unsigned short* xpl;   // x plane images [2][npix][Cin] (+ 16 B of zeros behind them)
     const unsigned short* dypl;  // dy plane images [2][npix][Cout]
@@ -36,24 +30,9 @@ struct Wg3Params {
     int nk, nchunk;              // k-ranges; 32-position chunks in all
 };
 
-__device__ __forceinline__ float wg3_scale_of_amax(float amax) {      // = koaf_gemm.hip scale_of_amax
-    if (!(amax > 0.f)) return 1.f;
-    const int e = min(max(__builtin_amdgcn_frexp_expf(amax), -100), 100);
-    return __builtin_ldexpf(1.f, 15 - e);
-}
-
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-// one LDS-DMA instruction: 64 lanes x 16 B from per-lane global addresses to the 1 KiB at LDS byte address lds_addr (see koaf_gemm.hip)
-__device__ __forceinline__ void wg3_dma16(const void* gsrc, unsigned lds_addr) {
-    const int la = __builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(la) : "memory", "m0");
-}
-#pragma clang diagnostic pop
-
 // LDS images: [position][64 channels] fp16, 128 B per position, 16-B chunks XOR-swizzled by the position
 // (chunk ^ 4 ((pos >> 1) & 1)): the transposing fragment reads (ds_read_b64_tr_b16) of four consecutive positions then
-// hit distinct banks wherever they start (koaf_gemm.hip PlaneKLoader / frag_load_kmd, 128-B rows).
+// hit distinct banks wherever they start (koaf_gemm_loaders.h PlaneKLoader / koaf_pieces.h frag_load_kmd, 128-B rows).
 template <int RC>
 __global__ void __launch_bounds__(768) wgrad3x3_ring_kernel(Wg3Params p) {
     constexpr int XPLANE = RC * 4096;            // bytes of one x ring plane (RC chunks x 32 positions x 128 B)
@@ -77,7 +56,7 @@ __global__ void __launch_bounds__(768) wgrad3x3_ring_kernel(Wg3Params p) {
     const int per = (p.nchunk + p.nk - 1) / p.nk;
     const int c0 = z * per, c1 = min(p.nchunk, c0 + per);
 
-    float alpha = 1.f / (p.x_scale * wg3_scale_of_amax(*p.dy_amax));
+    float alpha = 1.f / (p.x_scale * scale_of_amax(*p.dy_amax));
     if (!koaf_bits_finite(koaf_absbits(*p.dy_amax))) {
         alpha = __uint_as_float(0x7fc00000u);        // (a diverged dy: the whole gradient is NaN, as koaf_gemm does)
         if (b == 0 && t == 0) koaf_status_add(p.status, 1, 1u);
@@ -106,14 +85,14 @@ __global__ void __launch_bounds__(768) wgrad3x3_ring_kernel(Wg3Params p) {
             const unsigned dst = sx0 + (unsigned)(lm & (RC - 1)) * 4096u + (unsigned)pj * 1024u;
             const unsigned short* s0 = ok ? p.xpl + pix * p.Cin + (cit * 64 + lch) : p.xzero;
             const unsigned short* s1 = ok ? s0 + p.xps : p.xzero;
-            wg3_dma16(s0, dst);
-            wg3_dma16(s1, dst + XPLANE);
+            lds_dma16(s0, dst);
+            lds_dma16(s1, dst + XPLANE);
         } else {
             const unsigned dst = sdy0 + (unsigned)(((lm % 3) + 3) % 3) * DYSTAGE + (unsigned)pj * 1024u;
             const unsigned short* s0 = ok ? p.dypl + pix * p.Cout + (cot * 64 + lch) : p.dyzero;
             const unsigned short* s1 = ok ? s0 + p.dyps : p.dyzero;
-            wg3_dma16(s0, dst);
-            wg3_dma16(s1, dst + DYPLANE);
+            lds_dma16(s0, dst);
+            lds_dma16(s1, dst + DYPLANE);
         }
         // next chunk: 32 positions on
         ++lm;

@@ -1,10 +1,11 @@
-"""(build container, no GPU) register spills of the persistent / two-source GEMM instantiations: compiles koaf_gemm.hip with
--Rpass-analysis=kernel-resource-usage (3 min) and prints VGPRs / spilled VGPRs / scratch per instantiation that spills, against the
+"""(build container, no GPU) register spills of the persistent / two-source GEMM instantiations: compiles the GEMM family files
+(csrc/koaf_gemm*.hip, with the Makefile's own flags) with -Rpass-analysis=kernel-resource-usage (1 min) and prints VGPRs / spilled VGPRs / scratch per instantiation that spills, against the
 counts recorded when the round-4 regression was fixed (a 64-bit row index in the shared epilogue had cost every kernel ~30 VGPRs and
 the persistent 1x1 kernels 40-90 spilled registers: +40 ms per step, invisible in the build output).
     python scripts/check_spills.py"""
-import re, subprocess, sys
+import re, sys
 from pathlib import Path
+from compare_kernels import compile_commands, run_all
 CS = Path(__file__).resolve().parent.parent / "oaprogressionmmf_amd" / "csrc"
 RECORDED = {   # template arguments -> spilled VGPRs at the fixed build (koaf_gemm_kernel<BM, BN, AM, BMD, TFA, TFB, VEC, F16, NT, ACT, EMIT, SD>)
     "128,128,0,6,1,0,1,1,256,0,0,0": 7, "128,128,1,6,1,0,1,1,256,0,0,0": 35, "128,128,1,6,0,0,1,1,256,0,0,0": 14,
@@ -15,9 +16,9 @@ RECORDED = {   # template arguments -> spilled VGPRs at the fixed build (koaf_ge
     "128,128,13,6,1,0,1,1,256,0,1,2": 22, "128,128,13,6,2,0,1,1,256,0,0,2": 0, "128,128,13,6,3,0,1,1,256,0,0,2": 0,
     "128,64,13,6,2,0,1,1,256,0,0,2": 0, "128,64,13,6,3,0,1,1,256,0,0,2": 0,
 }
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-I../../include",
-       "-mllvm", "-amdgpu-mfma-vgpr-form", "-Rpass-analysis=kernel-resource-usage", "-c", "koaf_gemm.hip", "-o", "/tmp/koaf_gemm_spills.o"]
-txt = subprocess.run(cmd, cwd=CS, capture_output=True, text=True).stderr
+cmds = [c + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
+        for src, c in compile_commands(CS) if src.startswith("koaf_gemm")]
+txt = "".join(run_all(cmds, CS))
 bad = 0
 for b in txt.split("remark: Function Name: ")[1:]:
     name = b.split(" ")[0]

@@ -14,7 +14,7 @@ d = json.loads([ln for ln in open(O / "bench.log", errors="ignore") if ln.starts
 workload = tag.split("_")[0]
 
 
-GEMM_KERNELS = ("koaf_gemm_kernel", "wgrad3x3_ring_kernel")      # what bench.py's GEMM-family brackets launch (koaf_gemm.hip, koaf_wgrad3.hip)
+GEMM_KERNELS = ("koaf_gemm_kernel", "wgrad3x3_ring_kernel")      # what bench.py's GEMM-family brackets launch (koaf_gemm_kernel.h, koaf_wgrad3.hip)
 
 
 def kernel_sum(f, name):

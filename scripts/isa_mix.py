@@ -1,18 +1,18 @@
 """Instruction mix of the koaf_gemm_kernel main loops, from the device assembly (runs in the build container, no GPU):
-compiles csrc/koaf_gemm.hip with -S, finds for each requested instantiation the basic block holding the MFMAs and the
+compiles the GEMM family files csrc/koaf_gemm*.hip (the Makefile's flags) with -S, finds for each requested instantiation the basic block holding the MFMAs and the
 blocks of the same loop before it, and prints MFMA / vector / scalar / LDS / memory instruction counts per k-step and the
 most frequent vector opcodes (every block between the loop header and the MFMA block is summed, so code that runs only
 when the filter tap changes -- the dgrad gather -- is counted as if it ran every k-step).  Usage: python scripts/isa_mix.py [BM,BN,AM,BMD,TFA,TFB,VEC,F16,NT ...]
 (default: 1x1 and 3x3 forward with the fp32 loader, gather / halo / K-major plane-image kernels, fp32-loader weight gradient, dense bf16)."""
 import collections
 import re
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
+from compare_kernels import compile_commands, run_all
 
 ROOT = Path(__file__).resolve().parent.parent
-SRC = ROOT / "oaprogressionmmf_amd" / "csrc" / "koaf_gemm.hip"
+CS = ROOT / "oaprogressionmmf_amd" / "csrc"
 # BM,BN,AM,BMD,TFA,TFB,VEC,F16,NT (the template arguments of koaf_gemm_kernel; modes as in the source's enum)
 DEFAULT = ["128,128,0,6,1,0,1,1,256", "128,128,1,6,1,0,1,1,256", "128,128,7,6,0,0,1,1,256", "256,128,9,6,0,0,1,1,512",
            "128,128,10,11,0,0,1,1,256", "128,128,3,4,2,1,1,1,256", "128,128,0,0,0,0,1,0,256"]
@@ -37,11 +37,9 @@ def classify(ops):
 def main():
     sigs = sys.argv[1:] or DEFAULT
     with tempfile.TemporaryDirectory() as td:
-        out = Path(td) / "gemm.s"
-        subprocess.run(["/opt/rocm/bin/hipcc", "-S", "--offload-device-only", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-Wno-unused-function", f"-I{ROOT / 'include'}", "-mllvm", "-amdgpu-mfma-vgpr-form", str(SRC), "-o", str(out)],
-                       check=True, stderr=subprocess.DEVNULL)
-        txt = out.read_text().split("\n")
+        fam = [(src, c) for src, c in compile_commands(CS) if src.startswith("koaf_gemm")]
+        run_all([c + ["--cuda-device-only", "-S", src, "-o", f"{td}/{Path(src).stem}.s"] for src, c in fam], CS)
+        txt = [ln for f in sorted(Path(td).glob("*.s")) for ln in f.read_text().split("\n")]
     for sig in sigs:
         name = mangled(sig)
         start = [i for i, l in enumerate(txt) if l.startswith("_ZN") and name in l and l.rstrip().endswith("KoafGemm")]

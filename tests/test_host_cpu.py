@@ -414,3 +414,33 @@ def test_clock_per_kernel_reduction(tmp_path):
     k = json.loads(out.read_text())["kernels"]
     assert len(k) == 1 and k[0]["launches"] == 5 and k[0]["kernel"].startswith("koaf_gemm_kernel<256, 128, 9,")
     assert abs(k[0]["clock_ghz"] - 1.9) < 1e-3 and abs(k[0]["mfma_busy_frac_at_clock"] - 0.5) < 1e-3 and abs(k[0]["avg_us"] - 2000.0) < 1e-6
+
+
+def test_makefile_compiles_every_unit_once_with_the_matrix_pipe_flag():
+    """Every csrc/*.hip except the stamps unit goes into libkoaf.so exactly once, and every unit that receives the GEMM's
+    matrix-pipe code (koaf_gemm_kernel.h, directly or through another header; the attention kernel; the plane cutters) is built
+    with -amdgpu-mfma-vgpr-form: a unit that misses the flag compiles, passes every numerical test and is slower."""
+    import re
+    import shlex
+    csrc = ROOT / "oaprogressionmmf_amd" / "csrc"
+    dry = subprocess.run(["make", "-n", "-B", "-C", str(csrc)], check=True, capture_output=True, text=True).stdout
+    lines = [shlex.split(ln) for ln in dry.splitlines() if " -c " in ln]
+    compiled = [a[a.index("-c") + 1] for a in lines]
+    want = sorted(p.name for p in csrc.glob("*.hip") if p.name != "koaf_gemm_stamps.hip")
+    assert sorted(compiled) == want, (sorted(compiled), want)
+    link = [shlex.split(ln) for ln in dry.splitlines() if "-shared" in ln]
+    assert len(link) == 1 and link[0][-1] == "libkoaf.so"
+    assert sorted(a for a in link[0] if a.endswith(".o")) == sorted(n[:-4] + ".o" for n in want)
+
+    def headers(path, seen):
+        for h in re.findall(r'^#include "([^"/]+)"', path.read_text(), re.M):
+            if h not in seen and (csrc / h).exists():
+                seen.add(h)
+                headers(csrc / h, seen)
+        return seen
+
+    needs = [n for n in want if "koaf_gemm_kernel.h" in headers(csrc / n, set()) or n in ("koaf_attention.hip", "koaf_planes.hip")]
+    assert len(needs) >= 5 and "koaf_gemm.hip" in needs
+    for a in lines:
+        if a[a.index("-c") + 1] in needs:
+            assert "-amdgpu-mfma-vgpr-form" in a and a[a.index("-amdgpu-mfma-vgpr-form") - 1] == "-mllvm", a
