@@ -7,7 +7,8 @@
  *   koafusion/models/_core_trf.py:118-205               (Linear / LayerNorm / GELU / attention)
  *   koafusion/various/_losses.py:89-108                 (focal softmax-CE)
  *   koafusion/preproc/_pt.py:75-345                     (F.interpolate x0.5 downscale; the per-sample tensor transforms)
- *   torch.optim.Adam via koafusion/various/_optimizers.py:47-52
+ *   torch.optim.Adam / SGD / RMSprop via koafusion/various/_optimizers.py:47-52
+ *   nn.BCELoss / nn.BCEWithLogitsLoss via koafusion/various/_losses.py:111-117
  * Each entry point below names the reference call site it replaces.  All pointers are DEVICE
  * pointers to fp32 (unless stated), all tensors are dense; activations are NHWC ("(n,h,w,c)",
  * c fastest).  Nothing allocates; every call is asynchronous on `stream` (a hipStream_t passed as
@@ -26,7 +27,7 @@ extern "C" {
 #define KOAF_EINVAL (-1)
 #define KOAF_ELAUNCH (-2)
 
-int koaf_version(void);          /* 100 * major + 10 * minor: 190 = this header */
+int koaf_version(void);          /* 100 * major + 10 * minor: 200 = this header */
 const char* koaf_last_error(void);
 /* Numerics status words: a device uint32[4] (zeroed by the caller; NULL = off, the default) that kernels bump with atomics when
  *   [0] an activation operand left the fp16 range of the fixed activation scale and was CLAMPED (KOAF_ACT_SCALE: |x| > 4094), or
@@ -583,6 +584,40 @@ int koaf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  * sqrt(1 - beta2^step)} from the device scalars; hand `hyper` to koaf_adam_step (its host lr / step are then ignored). */
 int koaf_adam_hyper(int32_t* step, const float* lr, double beta1, double beta2, float* hyper, void* stream);
 int koaf_fill(float* p, float value, int64_t n, void* stream);
+
+/* ---- torch.optim.SGD over a flat arena (_optimizers.py:47-52, the "SGD" key) -------------------
+ * g' = (maximize ? -g : g) + weight_decay * p;  with a momentum: buf = first ? g' : momentum * buf + (1 - dampening) * g' and
+ * the step is g' + momentum * buf (nesterov) or buf;  without: the step is g';  p -= lr * step.  buf: the momentum buffer
+ * (NULL exactly when momentum == 0); `first`: this is the first update of these elements (buf is written, not read).
+ * hyper (nullable): device float[2] from koaf_optim_hyper -- lr and first then come from the device, the host values are
+ * ignored.  One pass: p, g (and buf) read once, p (and buf) written once. */
+int koaf_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, double momentum, double dampening,
+                  float weight_decay, int32_t nesterov, int32_t maximize, int32_t first, const float* hyper, void* stream);
+/* ---- torch.optim.RMSprop over a flat arena (_optimizers.py:47-52, the "RMSprop" key) -----------
+ * g' as above;  sq = alpha * sq + (1 - alpha) * g'^2;  centered (gavg non-NULL): gavg += (1 - alpha) * (g' - gavg) and
+ * avg = sqrt(sq - gavg^2) + eps, else avg = sqrt(sq) + eps;  with a momentum (buf non-NULL exactly when momentum > 0):
+ * buf = momentum * buf + g' / avg, p -= lr * buf;  without: p -= lr * g' / avg.  hyper (nullable): as for koaf_sgd_step
+ * (only lr is used). */
+int koaf_rmsprop_step(float* p, const float* g, float* sq, float* gavg, float* buf, int64_t n, float lr, double alpha, float eps,
+                      float weight_decay, double momentum, int32_t maximize, const float* hyper, void* stream);
+/* Device-resident step state of both, for captured (HIP-graph) train steps -- the counterpart of koaf_adam_hyper: ++*step;
+ * hyper[2] = {*lr, *step == 1 ? 1 : 0}. */
+int koaf_optim_hyper(int32_t* step, const float* lr, float* hyper, void* stream);
+
+/* ---- nn.BCELoss / nn.BCEWithLogitsLoss (_losses.py:111-117, the "bce_loss" / "bce_wlogits_loss" keys) ----
+ * x, target [n] (any equal shape, flattened), weight [n] (already expanded to x's shape) or NULL, pos_weight [C] or NULL (logits
+ * form only; C = the last dimension, n % C == 0).  Loss and gradient in one launch:
+ *   from_logits 0:  l = -w * (t * max(log x, -100) + (1 - t) * max(log(1 - x), -100)),  dl/dx = w * (x - t) / max((1 - x) * x, 1e-12)
+ *                   (torch's clamps).  A probability outside [0, 1], where torch raises a device assert, gets zero loss and
+ *                   zero gradient and is counted in status word [1].
+ *   from_logits 1:  l = w * ((1 - t) * x + (1 + (pw - 1) * t) * (log1p(exp(-|x|)) + max(-x, 0)))
+ * reduction 0: loss [n] per element; 1: mean, 2: sum (loss a scalar).  dx [n] = d loss / d x for an upstream gradient of 1 (it
+ * carries the mean's 1 / n).  ws: koaf_bce_ws(n) floats or NULL.  Up to 8192 elements one block does everything; beyond that,
+ * with a workspace, a grid of 4096-element blocks whose partial sums one block adds in index order (two fixed-order stages:
+ * the result does not depend on scheduling; without a workspace the one block walks everything). */
+int64_t koaf_bce_ws(int64_t n);
+int koaf_bce_loss(const float* x, const float* target, const float* weight, const float* pos_weight, float* loss, float* dx,
+                  int64_t n, int32_t C, int32_t from_logits, int32_t reduction, float* ws, void* stream);
 
 #ifdef __cplusplus
 }

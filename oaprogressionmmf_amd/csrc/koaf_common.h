@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/koaf.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -31,6 +32,19 @@ static inline int koaf_check_launch(const char* what) {
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// grid of the grid-stride element-wise kernels (256-thread blocks, `nvec` work items), capped in blocks per CU
+// (KOAF_EW_BLOCKS_PER_CU, default 32) over the chip's 256 CUs: one knob for koaf_elem.hip and koaf_optim.hip
+static inline int ew_blocks_per_cu() {
+    static const int v = [] { const char* e = getenv("KOAF_EW_BLOCKS_PER_CU"); int n = e ? atoi(e) : 32; return n < 1 ? 1 : n; }();
+    return v;
+}
+static inline unsigned ew_grid(int64_t nvec) {
+    int64_t b = cdiv64(nvec, 256);
+    if (b > 256 * ew_blocks_per_cu()) b = 256 * ew_blocks_per_cu();
+    if (b < 1) b = 1;
+    return (unsigned)b;
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

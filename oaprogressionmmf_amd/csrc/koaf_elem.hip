@@ -19,23 +19,11 @@ extern "C" const char* koaf_last_error(void) { return g_err; }
 static uint32_t* g_status = nullptr;
 uint32_t* koaf_status_ptr() { return g_status; }
 extern "C" int koaf_set_status_buffer(uint32_t* dev4) { g_status = dev4; return KOAF_OK; }
-extern "C" int koaf_version(void) { return 190; }   // 1.9: koaf_launch_log / koaf_launch_log_read (host-side record of the koaf_gemm launches, for tests); 1.8: koaf_set_stream (streamed kernel of the dense 1x1 convolutions, KoafGemm A mode M_KS); 1.7: KoafEmit / KoafGemm.out_planes (epilogue cuts the consumer's plane images), loss labels outside [0, C); 1.6: KoafTail.idt_sc / idt_sh (tails behind a downsample branch), koaf_stem_fwd statistics, koaf_stem_wgrad dy_apply, koaf_bn_bwd_reduce_pool
+extern "C" int koaf_version(void) { return 200; }   // 2.0: koaf_sgd_step / koaf_rmsprop_step / koaf_optim_hyper (koaf_optim.hip), koaf_bce_loss / koaf_bce_ws (koaf_bce.hip); 1.9: koaf_launch_log / koaf_launch_log_read (host-side record of the koaf_gemm launches, for tests); 1.8: koaf_set_stream (streamed kernel of the dense 1x1 convolutions, KoafGemm A mode M_KS); 1.7: KoafEmit / KoafGemm.out_planes (epilogue cuts the consumer's plane images), loss labels outside [0, C); 1.6: KoafTail.idt_sc / idt_sh (tails behind a downsample branch), koaf_stem_fwd statistics, koaf_stem_wgrad dy_apply, koaf_bn_bwd_reduce_pool
 
 namespace {
 
 constexpr int EB = 256;  // elementwise block
-
-// grid cap of the grid-stride element-wise kernels, in blocks per CU (KOAF_EW_BLOCKS_PER_CU, default 32)
-inline int ew_blocks_per_cu() {
-    static const int v = [] { const char* e = getenv("KOAF_EW_BLOCKS_PER_CU"); int n = e ? atoi(e) : 32; return n < 1 ? 1 : n; }();
-    return v;
-}
-inline unsigned ew_grid(int64_t nvec) {
-    int64_t b = cdiv64(nvec, EB);
-    if (b > 256 * ew_blocks_per_cu()) b = 256 * ew_blocks_per_cu();
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
 
 // ------------------------------------------------------------------------------------------------
 // column partial sums over a [rows][C] tensor.  Block (256 thr) owns a chunk of <= 1024 columns and

@@ -245,6 +245,23 @@ class LossFn(torch.autograd.Function):
         return dl, None, None, None, None, None
 
 
+class BCEFn(torch.autograd.Function):
+    """nn.BCELoss / nn.BCEWithLogitsLoss forward + backward in one kernel (koafusion/various/_losses.py:111-117).
+    weight: already of the input's shape, or None; pos_weight: (C,) = the input's last dimension, or None."""
+
+    @staticmethod
+    def forward(ctx, x, target, weight, pos_weight, from_logits, reduction):
+        loss, dx = ops.bce_loss(x.contiguous(), target.contiguous(), weight, pos_weight, from_logits=from_logits,
+                                reduction=reduction)
+        ctx.dx = dx
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        # (reduction 'none': g has the input's shape -- an elementwise product; otherwise a scalar)
+        return ctx.dx * g, None, None, None, None, None
+
+
 def linear(x, weight, bias=None, residual=None):
     return LinearFn.apply(x, weight, bias, residual)
 

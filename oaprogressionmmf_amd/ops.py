@@ -813,6 +813,57 @@ def adam_hyper(step, lr, b1, b2, hyper):
     check(lib().koaf_adam_hyper(step.data_ptr(), _ptr(lr), b1, b2, _ptr(hyper), _stream()), "adam_hyper")
 
 
+def sgd_step(p, g, buf, n, lr, momentum=0.0, dampening=0.0, wd=0.0, nesterov=False, maximize=False, first=False, hyper=None):
+    """torch.optim.SGD's update over n elements in place; buf: the momentum buffer (None without a momentum), written but not
+    read when `first`; hyper: optional device float[2] from optim_hyper() -- lr and first then come from the device"""
+    check(lib().koaf_sgd_step(_ptr(p), _ptr(g), _ptr(buf), n, lr, momentum, dampening, wd, 1 if nesterov else 0,
+                              1 if maximize else 0, 1 if first else 0, _ptr(hyper), _stream()), "sgd_step")
+
+
+def rmsprop_step(p, g, sq, n, lr, alpha=0.99, eps=1e-8, wd=0.0, momentum=0.0, gavg=None, buf=None, maximize=False, hyper=None):
+    """torch.optim.RMSprop's update over n elements in place; gavg: the gradient average of the centered form (None: plain),
+    buf: the momentum buffer (None exactly when momentum == 0); hyper: optional device float[2] from optim_hyper()"""
+    check(lib().koaf_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), _ptr(gavg), _ptr(buf), n, lr, alpha, eps, wd, momentum,
+                                  1 if maximize else 0, _ptr(hyper), _stream()), "rmsprop_step")
+
+
+def optim_hyper(step, lr, hyper):
+    """++step (int32 device scalar); hyper[2] = {lr, step == 1} from the device scalars (captured SGD / RMSprop steps)"""
+    if step.dtype != torch.int32 or not step.is_cuda:
+        raise KoafError("optim_hyper: step is an int32 device scalar")
+    check(lib().koaf_optim_hyper(step.data_ptr(), _ptr(lr), _ptr(hyper), _stream()), "optim_hyper")
+
+
+_BCE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def bce_loss(x, target, weight=None, pos_weight=None, from_logits=False, reduction="mean"):
+    """x, target, weight (or None): contiguous fp32 tensors of one shape; pos_weight (C,) = x's last dimension, or None
+    -> (loss, dx): loss a scalar (mean | sum) or of x's shape (none); dx = d loss / d x for an upstream gradient of 1"""
+    if reduction not in _BCE_REDUCTIONS:
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+    for t in (x, target, weight, pos_weight):
+        _ptr(t)                                  # (CPU tensors stop here)
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise KoafError("bce_loss: contiguous fp32 tensors only")
+    n = x.numel()
+    if n == 0:
+        raise KoafError("bce_loss: empty input")
+    C = int(x.shape[-1]) if x.dim() > 0 else 1
+    for name, t in (("target", target), ("weight", weight)):
+        if t is not None and tuple(t.shape) != tuple(x.shape):
+            raise KoafError(f"bce_loss: {name} shape {tuple(t.shape)} does not match the input's {tuple(x.shape)}")
+    if pos_weight is not None and (not from_logits or pos_weight.numel() != C):
+        raise KoafError("bce_loss: pos_weight belongs to the logits form and has the input's last dimension")
+    loss = torch.empty_like(x) if reduction == "none" else _empty((), x)
+    dx = torch.empty_like(x)
+    nws = lib().koaf_bce_ws(n) if reduction != "none" else 0
+    ws = _empty((nws,), x) if nws > 0 else None
+    check(lib().koaf_bce_loss(_ptr(x), _ptr(target), _ptr(weight), _ptr(pos_weight), _ptr(loss), _ptr(dx), n, C,
+                              1 if from_logits else 0, _BCE_REDUCTIONS[reduction], _ptr(ws), _stream()), "bce_loss")
+    return loss, dx
+
+
 def build_weight_planes(w, R, taps, C):
     """(F, D, amax) fp16 plane images (int16 tensors) + device scalar max |w| of ONE weight w [R][taps][C] (packed conv
     weight): what arena.ParamArena keeps for every convolution weight of a model, for callers without an arena (tests,

@@ -58,13 +58,14 @@ class GraphedTrainStep(object):
     The first `warmup` calls run the step eagerly (arena adoption, optimizer state, allocator warm-up: real training steps),
     the next call captures it into a HIP graph and replays it, later calls only copy the batch into the captured input
     buffers and replay.  Eager and replayed steps are the same kernels on the same device-resident step state, so a run
-    is bit-identical whether or not (and when) it switches to replay.  `optimizer` must be Adam/AdamW(capturable=True);
+    is bit-identical whether or not (and when) it switches to replay.  `optimizer` must be a registry optimizer (Adam / AdamW / SGD / RMSprop) with capturable=True;
     `model` a registry model on one GPU (the RCCL exchange of DataParallelRCCL is not captured).  The returned tensors are
     owned by the graph and overwritten by the next call.  Learning-rate changes (schedulers) are picked up at every call."""
 
     def __init__(self, model, loss_fn, optimizer, example_xs, example_ys, downscale=None, warmup=2, seed=None):
         if not getattr(optimizer, "capturable", False):
-            raise RuntimeError("GraphedTrainStep needs Adam/AdamW(capturable=True): step count and learning rate on the device")
+            raise RuntimeError("GraphedTrainStep needs a registry optimizer with capturable=True (Adam / AdamW / SGD / RMSprop): step count "
+                               "and learning rate on the device")
         if hasattr(model, "reduce_gradients"):
             raise RuntimeError("GraphedTrainStep captures single-GPU steps (the RCCL gradient exchange is not captured)")
         self.model, self.loss_fn, self.opt, self.downscale = model, loss_fn, optimizer, downscale
