@@ -27,7 +27,10 @@ extern "C" {
 #define KOAF_EINVAL (-1)
 #define KOAF_ELAUNCH (-2)
 
-int koaf_version(void);          /* 100 * major + 10 * minor: 200 = this header */
+/* The ABI version of this header, 100 * major + 10 * minor.  Any change to a prototype or a struct below bumps it: the binding
+ * refuses a library whose koaf_version() differs from the header it parsed. */
+#define KOAF_VERSION 200
+int koaf_version(void);          /* KOAF_VERSION of the header the library was built from */
 const char* koaf_last_error(void);
 /* Numerics status words: a device uint32[4] (zeroed by the caller; NULL = off, the default) that kernels bump with atomics when
  *   [0] an activation operand left the fp16 range of the fixed activation scale and was CLAMPED (KOAF_ACT_SCALE: |x| > 4094), or

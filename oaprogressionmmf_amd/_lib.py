@@ -1,10 +1,13 @@
 """ctypes binding of libkoaf.so (the C ABI declared in include/koaf.h).
 
-The prototypes are parsed from the header itself, so the Python side cannot drift from the C side.
+Struct layouts, prototypes and constants are all parsed from the header itself, so the Python side cannot drift from the C
+side, and `lib()` refuses a library whose koaf_version() is not the header's KOAF_VERSION: a stale build read through newer
+descriptors would shift arguments and write through wild device pointers.
 There is no CPU fallback: if the library is missing, `lib()` raises -- the product path must fail
 loudly rather than silently run something else.
 """
 import ctypes
+import functools
 import os
 import re
 from pathlib import Path
@@ -14,174 +17,12 @@ HEADER = _ROOT.parent / "include" / "koaf.h"
 LIB_PATH = _ROOT / "csrc" / "libkoaf.so"
 
 
-class KoafOperand(ctypes.Structure):
-    _fields_ = [
-        ("ptr", ctypes.c_void_p),
-        ("ld", ctypes.c_int64),
-        ("bs0", ctypes.c_int64),
-        ("bs1", ctypes.c_int64),
-        ("tap_stride", ctypes.c_int64),
-        ("tap_stride_h", ctypes.c_int64),
-        ("kind", ctypes.c_int32),
-        ("gather", ctypes.c_int32),
-        ("H", ctypes.c_int32),
-        ("W", ctypes.c_int32),
-        ("C", ctypes.c_int32),
-        ("CS", ctypes.c_int32),
-        ("PH", ctypes.c_int32),
-        ("PW", ctypes.c_int32),
-        ("KH", ctypes.c_int32),
-        ("KW", ctypes.c_int32),
-        ("stride", ctypes.c_int32),
-        ("pad", ctypes.c_int32),
-        ("pad_w", ctypes.c_int32),
-        ("_pad1", ctypes.c_int32),
-        ("tf", ctypes.c_int32),
-        ("tf_bs", ctypes.c_int32),
-        ("sc", ctypes.c_void_p),
-        ("sh", ctypes.c_void_p),
-        ("planes", ctypes.c_void_p),
-        ("plane_stride", ctypes.c_int64),
-        ("amax", ctypes.c_void_p),
-        ("fscale", ctypes.c_float),
-        ("_pad4", ctypes.c_int32),
-        ("ptr2", ctypes.c_void_p),
-        ("sc2", ctypes.c_void_p),
-        ("zeros", ctypes.c_void_p),
-        ("side", ctypes.c_void_p),
-        ("sh2", ctypes.c_void_p),
-    ]
-
-
-class KoafGemm(ctypes.Structure):
-    _fields_ = [
-        ("A", KoafOperand),
-        ("B", KoafOperand),
-        ("M", ctypes.c_int32),
-        ("N", ctypes.c_int32),
-        ("K", ctypes.c_int32),
-        ("nb0", ctypes.c_int32),
-        ("nb1", ctypes.c_int32),
-        ("splitk", ctypes.c_int32),
-        ("bm", ctypes.c_int32),
-        ("bn", ctypes.c_int32),
-        ("C", ctypes.c_void_p),
-        ("ldc", ctypes.c_int64),
-        ("cbs0", ctypes.c_int64),
-        ("cbs1", ctypes.c_int64),
-        ("alpha", ctypes.c_float),
-        ("prec", ctypes.c_int32),
-        ("bias", ctypes.c_void_p),
-        ("residual", ctypes.c_void_p),
-        ("ldr", ctypes.c_int64),
-        ("rbs0", ctypes.c_int64),
-        ("rbs1", ctypes.c_int64),
-        ("stats", ctypes.c_void_p),
-        ("stats_ld", ctypes.c_int64),
-        ("stats_bs", ctypes.c_int64),
-        ("cmap", ctypes.c_int32),
-        ("cm_PH", ctypes.c_int32),
-        ("cm_PW", ctypes.c_int32),
-        ("cm_H", ctypes.c_int32),
-        ("cm_W", ctypes.c_int32),
-        ("cm_py", ctypes.c_int32),
-        ("cm_px", ctypes.c_int32),
-        ("_pad2", ctypes.c_int32),
-        ("bnb_mode", ctypes.c_int32),
-        ("fmt", ctypes.c_int32),
-        ("bnb_c", ctypes.c_void_p),
-        ("bnb_y", ctypes.c_void_p),
-        ("bnb_sc", ctypes.c_void_p),
-        ("bnb_sh", ctypes.c_void_p),
-        ("bnb_mean", ctypes.c_void_p),
-        ("bnb_invstd", ctypes.c_void_p),
-        ("bnb2_c", ctypes.c_void_p),
-        ("bnb2_mean", ctypes.c_void_p),
-        ("bnb2_invstd", ctypes.c_void_p),
-        ("bnb_part", ctypes.c_void_p),
-        ("bnb_amax", ctypes.c_void_p),
-        ("m_base", ctypes.c_int32),
-        ("part_row0", ctypes.c_int32),
-        ("stats_shift", ctypes.c_void_p),
-        ("status", ctypes.c_void_p),
-        ("act16", ctypes.c_int32),
-        ("_pad5", ctypes.c_int32),
-        ("out_planes", ctypes.c_void_p),
-        ("out_sc", ctypes.c_void_p),
-        ("out_sh", ctypes.c_void_p),
-        ("out_ps", ctypes.c_int64),
-    ]
-
-
-class KoafBnb(ctypes.Structure):
-    _fields_ = [
-        ("mode", ctypes.c_int32),
-        ("_pad", ctypes.c_int32),
-        ("dz_amax", ctypes.c_void_p),
-        ("c", ctypes.c_void_p),
-        ("y", ctypes.c_void_p),
-        ("sc", ctypes.c_void_p),
-        ("sh", ctypes.c_void_p),
-        ("mean", ctypes.c_void_p),
-        ("invstd", ctypes.c_void_p),
-        ("c2", ctypes.c_void_p),
-        ("mean2", ctypes.c_void_p),
-        ("invstd2", ctypes.c_void_p),
-    ]
-
-
-class KoafWPlane(ctypes.Structure):
-    _fields_ = [
-        ("src_off", ctypes.c_int64),
-        ("f_off", ctypes.c_int64),
-        ("d_off", ctypes.c_int64),
-        ("tile0", ctypes.c_int64),
-        ("R", ctypes.c_int32),
-        ("taps", ctypes.c_int32),
-        ("C", ctypes.c_int32),
-        ("Kp", ctypes.c_int32),
-        ("Rp", ctypes.c_int32),
-        ("_pad", ctypes.c_int32),
-    ]
-
-
-class KoafWImg(ctypes.Structure):
-    _fields_ = [("f", ctypes.c_void_p), ("d", ctypes.c_void_p), ("amax", ctypes.c_void_p)]
-
-
-class KoafTail(ctypes.Structure):
-    _fields_ = [("idt", ctypes.c_void_p), ("y_out", ctypes.c_void_p), ("idt_sc", ctypes.c_void_p), ("idt_sh", ctypes.c_void_p)]
-
-
-class KoafEmit(ctypes.Structure):
-    _fields_ = [("planes", ctypes.c_void_p), ("sc", ctypes.c_void_p), ("sh", ctypes.c_void_p)]
-
-
-class KoafBnApply(ctypes.Structure):
-    _fields_ = [("dz", ctypes.c_void_p), ("c", ctypes.c_void_p), ("coef", ctypes.c_void_p), ("amax", ctypes.c_void_p)]
-
-
-class KoafLaunchRec(ctypes.Structure):
-    _fields_ = [
-        ("variant", ctypes.c_char * 24),
-        ("bm", ctypes.c_int32),
-        ("bn", ctypes.c_int32),
-        ("tiles", ctypes.c_int32),
-        ("grid_x", ctypes.c_int32),
-        ("splitk", ctypes.c_int32),
-        ("nbatch", ctypes.c_int32),
-        ("fmt", ctypes.c_int32),
-        ("a_tf", ctypes.c_int32),
-        ("b_tf", ctypes.c_int32),
-        ("act16", ctypes.c_int32),
-        ("M", ctypes.c_int32),
-        ("N", ctypes.c_int32),
-        ("K", ctypes.c_int32),
-        ("emit", ctypes.c_int32),
-    ]
+class KoafError(RuntimeError):
+    pass
 
 
 _SCALARS = {
+    "char": ctypes.c_char,
     "int": ctypes.c_int,
     "int32_t": ctypes.c_int32,
     "int64_t": ctypes.c_int64,
@@ -192,36 +33,66 @@ _SCALARS = {
 }
 
 
+@functools.lru_cache(maxsize=None)
+def _text(path):
+    """the header without its comments (read once per process)"""
+    return re.sub(r"/\*.*?\*/", " ", Path(path).read_text(), flags=re.S)
+
+
+_TYPEDEF = r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;"
+
+
+def _parse_structs(text):
+    """-> {name: ctypes.Structure subclass} for every `typedef struct NAME { ... } NAME;`, in declaration order"""
+    structs = {}
+    for m in re.finditer(_TYPEDEF, text):
+        name, fields = m.group(1), []
+        if name != m.group(3):
+            raise KoafError(f"koaf.h: typedef struct {name} is named {m.group(3)}")
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):
+            base, rest = re.match(r"\s*(\w*)(.*)", re.sub(r"\bconst\b", " ", decl), flags=re.S).groups()
+            for d in rest.split(","):               # `int32_t H, W, C;`  `const float* ptr;`  `char variant[24];`
+                dm = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d)
+                if dm is None or not (dm.group(1) or base in structs or base in _SCALARS):
+                    raise KoafError(f"koaf.h: cannot read field `{decl}` of {name}")
+                t = ctypes.c_void_p if dm.group(1) else structs.get(base) or _SCALARS[base]
+                fields.append((dm.group(2), t * int(dm.group(3)) if dm.group(3) else t))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    if len(structs) != len(re.findall(r"\btypedef\b", text)):
+        raise KoafError(f"koaf.h: only {sorted(structs)} of its typedefs could be read")
+    return structs
+
+
+STRUCTS = _parse_structs(_text(HEADER))
+KoafOperand = STRUCTS["KoafOperand"]
+KoafGemm = STRUCTS["KoafGemm"]
+KoafLaunchRec = STRUCTS["KoafLaunchRec"]
+KoafWPlane = STRUCTS["KoafWPlane"]
+KoafWImg = STRUCTS["KoafWImg"]
+KoafBnApply = STRUCTS["KoafBnApply"]
+KoafTail = STRUCTS["KoafTail"]
+KoafEmit = STRUCTS["KoafEmit"]
+KoafBnb = STRUCTS["KoafBnb"]
+
+
 def _ctype(decl: str):
-    decl = decl.strip()
-    if "*" in decl:
-        base = decl.replace("const", "").replace("*", "").split()[0]
-        if base == "KoafGemm":
-            return ctypes.POINTER(KoafGemm)
-        if base == "KoafBnb":
-            return ctypes.POINTER(KoafBnb)
-        if base == "KoafWImg":
-            return ctypes.POINTER(KoafWImg)
-        if base == "KoafBnApply":
-            return ctypes.POINTER(KoafBnApply)
-        if base == "KoafTail":
-            return ctypes.POINTER(KoafTail)
-        if base == "KoafEmit":
-            return ctypes.POINTER(KoafEmit)
-        if base == "KoafLaunchRec":
-            return ctypes.POINTER(KoafLaunchRec)
-        if base == "char":
-            return ctypes.c_char_p
-        return ctypes.c_void_p
-    toks = decl.replace("const", "").split()
+    toks = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split()
+    if "*" in toks:
+        if toks[0] in STRUCTS:
+            return ctypes.POINTER(STRUCTS[toks[0]])
+        return ctypes.c_char_p if toks[0] == "char" else ctypes.c_void_p
     return _SCALARS[toks[0]]
 
 
-def parse_header(path=HEADER):
+def defines(path=None):
+    """-> {name: int | float} for every numeric `#define KOAF_...` of koaf.h (KOAF_OK, KOAF_VERSION, KOAF_ACT_SCALE, ...)"""
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(KOAF_\w+)[ \t]+\(?(-?\d+(\.\d*f?)?)\)?[ \t]*$", _text(path or HEADER), flags=re.M)
+    return {name: float(val.rstrip("f")) if frac else int(val) for name, val, frac in found}
+
+
+def parse_header(path=None):
     """-> {name: (restype, [argtypes])} for every function prototype in koaf.h"""
-    text = Path(path).read_text()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = re.sub(r"typedef struct.*?\}\s*\w+;", " ", text, flags=re.S)
+    text = re.sub(_TYPEDEF, " ", _text(path or HEADER))
     text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)          # preprocessor lines
     protos = {}
     for m in re.finditer(r"([\w\s\*]+?)\b(koaf_\w+)\s*\(([^)]*)\)\s*;", text):
@@ -242,12 +113,8 @@ def parse_header(path=HEADER):
 _LIB = None
 
 
-class KoafError(RuntimeError):
-    pass
-
-
 def lib():
-    """Load libkoaf.so (once).  Raises if the HIP extension has not been built."""
+    """Load libkoaf.so (once).  Raises if the HIP extension has not been built, or was built from another koaf.h."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -257,6 +124,13 @@ def lib():
             f"libkoaf.so not found at {path}: build it with `python -c 'import __graft_entry__ as g; "
             f"g.build()'` or `make -C oaprogressionmmf_amd/csrc` -- there is no CPU fallback")
     handle = ctypes.CDLL(str(path))
+    # koaf_version(void) is the one signature that can never move: ask it before any other prototype is trusted
+    handle.koaf_version.restype, handle.koaf_version.argtypes = ctypes.c_int, []
+    want, got = defines()["KOAF_VERSION"], handle.koaf_version()
+    if got != want:
+        raise KoafError(
+            f"{path} is ABI version {got}, {HEADER} declares {want}: the descriptors would not line up -- rebuild the "
+            f"library with `make -C oaprogressionmmf_amd/csrc`")
     for name, (restype, argtypes) in parse_header().items():
         fn = getattr(handle, name)  # AttributeError if a declared symbol is missing
         fn.restype = restype

@@ -86,8 +86,8 @@ class ParamArena:
 
     # ---- weight plane images ------------------------------------------------------------------------------------
     def _build_plane_table(self, module):
+        from . import ops
         from ._lib import KoafWPlane
-        rup = lambda v, a: (v + a - 1) // a * a
         ents, off, tile0, seen = [], 0, 0, set()
         for m in module.modules():
             if isinstance(m, nn.Conv2d):
@@ -100,14 +100,10 @@ class ParamArena:
             if id(w) in seen or id(w) not in self.slots:
                 continue
             seen.add(id(w))
-            Kp, Rp = rup(taps * C, 32), rup(R, 32)
-            f_off = off
-            off += rup(2 * R * Kp, 64)
-            d_off = off
-            off += rup(2 * C * taps * Rp, 64)
-            ents.append((w, KoafWPlane(src_off=self.slots[id(w)][0], f_off=f_off, d_off=d_off, tile0=tile0, R=R, taps=taps,
-                                       C=C, Kp=Kp, Rp=Rp)))
-            tile0 += ((R + 31) // 32) * taps * ((C + 31) // 32)
+            ent, nf, nd, ntiles = ops.wplane_entry(R, taps, C, src_off=self.slots[id(w)][0], f_off=off, tile0=tile0)
+            ents.append((w, ent, nf, nd))
+            off = ent.d_off + _round_up(nd)
+            tile0 += ntiles
         self._plane_tiles = tile0
         self._plane_n = len(ents)
         if not ents:
@@ -115,12 +111,11 @@ class ParamArena:
             return
         self.W = torch.zeros(off, device=self.device, dtype=torch.int16)
         self.Wamax = torch.zeros(len(ents), device=self.device, dtype=torch.float32)     # max |w| per weight
-        arr = (KoafWPlane * len(ents))(*[e for _, e in ents])
+        arr = (KoafWPlane * len(ents))(*[e for _, e, _, _ in ents])
         self._plane_tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-        for i, (w, e) in enumerate(ents):
-            w._koaf_wimg = (self.W[e.f_off:e.f_off + 2 * e.R * e.Kp], self.W[e.d_off:e.d_off + 2 * e.C * e.taps * e.Rp],
-                            self.Wamax[i:i + 1])
-        self._plane_params = [w for w, _ in ents]
+        for i, (w, e, nf, nd) in enumerate(ents):
+            w._koaf_wimg = (self.W[e.f_off:e.f_off + nf], self.W[e.d_off:e.d_off + nd], self.Wamax[i:i + 1])
+        self._plane_params = [w for w, _, _, _ in ents]
 
     def _stamp(self):
         return (self.epoch, self.P._version, sum(p._version for p in self._plane_params))
@@ -135,10 +130,7 @@ class ParamArena:
         # previous replay's optimizer step left, whatever the host-side stamp of the capturing call says)
         if st == self._plane_stamp and not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
             return
-        from ._lib import check, lib
-        check(lib().koaf_wplanes_build(self.P.data_ptr(), self.W.data_ptr(), self.Wamax.data_ptr(), self._plane_tab.data_ptr(),
-                                       self._plane_n, self._plane_tiles, torch.cuda.current_stream().cuda_stream),
-              "wplanes_build")
+        ops.wplanes_build(self.P, self.W, self.Wamax, self._plane_tab, self._plane_n, self._plane_tiles)
         self._plane_stamp = st
 
     @staticmethod

@@ -35,20 +35,13 @@ class _EmbedFn(torch.autograd.Function):
         B, n, D = dy.shape
         dy = dy.contiguous()
         pos, cls_token, ncls = ctx.pos, ctx.cls_token, ctx.ncls
-        from .._lib import lib, check
-        L = lib()
         if pos.requires_grad:
             g, acc = grad_target(pos)
-            ws = torch.empty(max(L.koaf_colsum_ws(B, n * D), 1), device=dy.device)
-            check(L.koaf_colsum(dy.data_ptr(), g.data_ptr(), B, n * D, ws.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream), "colsum(pos)")
+            ops.colsum(dy, g, B, n * D, "colsum(pos)")
             deliver_grad(pos, g, acc)
         if cls_token is not None and cls_token.requires_grad:
             g, acc = grad_target(cls_token)
-            dc = dy[:, :ncls].contiguous()
-            ws = torch.empty(max(L.koaf_colsum_ws(B, ncls * D), 1), device=dy.device)
-            check(L.koaf_colsum(dc.data_ptr(), g.data_ptr(), B, ncls * D, ws.data_ptr(),
-                                torch.cuda.current_stream().cuda_stream), "colsum(cls)")
+            ops.colsum(dy[:, :ncls].contiguous(), g, B, ncls * D, "colsum(cls)")
             deliver_grad(cls_token, g, acc)
         return dy[:, ncls:], None, None
 

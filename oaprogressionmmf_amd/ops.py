@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from ._lib import KoafBnApply, KoafBnb, KoafEmit, KoafGemm, KoafError, KoafLaunchRec, KoafTail, KoafWImg, check, lib
+from ._lib import KoafBnApply, KoafBnb, KoafEmit, KoafGemm, KoafError, KoafLaunchRec, KoafTail, KoafWImg, KoafWPlane, check, defines, lib
 
 _i32 = ctypes.c_int32
 
@@ -21,7 +21,7 @@ CONV_F16 = os.environ.get("KOAF_CONV_FMT", "f16") != "bf16"
 # activation plane images for the gathered (3x3) convolution kernels (koaf_act_planes); KOAF_APLANES=0: fp32 loaders
 APLANES_MASK = int(os.environ.get("KOAF_APLANES", "7"))     # bit 0 forward, 1 data gradient, 2 weight gradient
 APLANES = APLANES_MASK != 0
-ACT_SCALE = 16.0        # koaf.h KOAF_ACT_SCALE
+ACT_SCALE = defines()["KOAF_ACT_SCALE"]      # the fixed activation scale of the fp16 scheme (koaf.h)
 # Forward plane images of up to this many 16-bit elements are kept on the convolution's output for its weight gradient
 # (saves re-cutting them).  Off by default: the mixed lifetimes fragment the caching allocator's pool -- the headline
 # step's reserved memory went from 240 to 265 GB (of 288) for 1 % of its time with everything kept, and still to 264 GB
@@ -779,6 +779,20 @@ def add(a, b):
     return out
 
 
+def colsum(x, out, rows, C, what="colsum"):
+    """out [C] = column sums of x [rows][C] (bias-like gradients)"""
+    L = lib()
+    n = L.koaf_colsum_ws(rows, C)
+    ws = _empty((n,), x) if n > 0 else None
+    check(L.koaf_colsum(_ptr(x), _ptr(out), rows, C, _ptr(ws), _stream()), what)
+
+
+def softmax_rows_(x):
+    """in-place row softmax of a contiguous fp32 (rows, n) device tensor"""
+    check(lib().koaf_softmax_rows(_ptr(x), x.shape[0], x.shape[1], _stream()), "softmax_rows")
+    return x
+
+
 def focal_loss(logits, target, gamma, mean=True, focal=True, class_weight=None):
     """logits (B, C[, d0, d1, ...]) contiguous, target (B[, d0, d1, ...]) int64, class_weight (C,) or None -> (loss, dlogits)"""
     B, C = logits.shape[0], logits.shape[1]
@@ -864,22 +878,39 @@ def bce_loss(x, target, weight=None, pos_weight=None, from_logits=False, reducti
     return loss, dx
 
 
+def _rup(v, a):
+    return (v + a - 1) // a * a
+
+
+def wplane_entry(R, taps, C, src_off=0, f_off=0, tile0=0):
+    """-> (KoafWPlane, nf, nd, ntiles): the table entry of one weight [R][taps][C] (koaf.h koaf_wplanes_build) whose F image
+    (nf 16-bit elements) starts at f_off and whose D image (nd elements) follows at the next multiple of 64, and the tiles
+    it adds to the table's running count"""
+    Kp, Rp = _rup(taps * C, 32), _rup(R, 32)
+    nf, nd = 2 * R * Kp, 2 * C * taps * Rp
+    ent = KoafWPlane(src_off=src_off, f_off=f_off, d_off=f_off + _rup(nf, 64), tile0=tile0, R=R, taps=taps, C=C, Kp=Kp, Rp=Rp)
+    return ent, nf, nd, (Rp // 32) * taps * (_rup(C, 32) // 32)
+
+
+def wplanes_build(base, planes, amax, table, n, ntiles):
+    """cut the plane images of the `n` weights that `table` (device bytes of KoafWPlane entries) describes: floats from `base`,
+    images into `planes` (int16), max |w| per weight into `amax`"""
+    if not planes.is_cuda or planes.dtype != torch.int16:
+        raise KoafError("weight plane images are int16 (fp16 bit patterns) tensors on the HIP device")
+    check(lib().koaf_wplanes_build(_ptr(base), planes.data_ptr(), _ptr(amax), ctypes.cast(_ptr(table), ctypes.POINTER(KoafWPlane)),
+                                   n, ntiles, _stream()), "wplanes_build")
+
+
 def build_weight_planes(w, R, taps, C):
     """(F, D, amax) fp16 plane images (int16 tensors) + device scalar max |w| of ONE weight w [R][taps][C] (packed conv
     weight): what arena.ParamArena keeps for every convolution weight of a model, for callers without an arena (tests,
     micro-benchmarks)."""
-    from ._lib import KoafWPlane
-    Kp, Rp = (taps * C + 31) // 32 * 32, (R + 31) // 32 * 32
-    nf, nd = 2 * R * Kp, 2 * C * taps * Rp
-    d_off = (nf + 63) // 64 * 64
-    planes = torch.zeros(d_off + nd, device=w.device, dtype=torch.int16)
+    ent, nf, nd, ntiles = wplane_entry(R, taps, C)
+    planes = torch.zeros(ent.d_off + nd, device=w.device, dtype=torch.int16)
     amax = torch.zeros(1, device=w.device, dtype=torch.float32)
-    ent = KoafWPlane(src_off=0, f_off=0, d_off=d_off, tile0=0, R=R, taps=taps, C=C, Kp=Kp, Rp=Rp)
     tab = torch.frombuffer(bytearray(bytes(ent)), dtype=torch.uint8).to(w.device)
-    ntiles = ((R + 31) // 32) * taps * ((C + 31) // 32)
-    check(lib().koaf_wplanes_build(_ptr(w), planes.data_ptr(), _ptr(amax), tab.data_ptr(), 1, ntiles, _stream()),
-          "wplanes_build")
-    return planes[:nf], planes[d_off:d_off + nd], amax
+    wplanes_build(w, planes, amax, tab, 1, ntiles)
+    return planes[:nf], planes[ent.d_off:ent.d_off + nd], amax
 
 
 def gemm(desc: KoafGemm):

@@ -55,7 +55,7 @@ def softmax_rows_(x):
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 2):
         raise KoafError("softmax_rows_: contiguous fp32 (rows, n) device tensor required")
     if x.shape[0]:
-        ops.check(ops.lib().koaf_softmax_rows(x.data_ptr(), x.shape[0], x.shape[1], ops._stream()), "softmax_rows")
+        ops.softmax_rows_(x)
     return x
 
 

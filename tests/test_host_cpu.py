@@ -7,6 +7,7 @@
 """
 import ctypes
 import json
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -35,17 +36,57 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layout_matches_c(tmp_path):
+    """every struct of koaf.h, every field: sizeof / offsetof as gcc lays them out == the ctypes classes parsed from the header"""
     from oaprogressionmmf_amd import _lib
+    structs = _lib.STRUCTS
+    assert len(structs) == len(re.findall(r"typedef\s+struct", _lib.HEADER.read_text())) == 9
+    for n in ("KoafOperand", "KoafGemm", "KoafLaunchRec", "KoafWPlane", "KoafWImg", "KoafBnApply", "KoafTail", "KoafEmit", "KoafBnb"):
+        assert getattr(_lib, n) is structs[n]
+    py = {f"sizeof({n})": ctypes.sizeof(c) for n, c in structs.items()}
+    for n, c in structs.items():
+        for f, _ in c._fields_:
+            py[f"offsetof({n},{f})"] = getattr(c, f).offset
+            py[f"sizeof((({n}*)0)->{f})"] = getattr(c, f).size
+    assert len(py) == 9 + 2 * sum(len(c._fields_) for c in structs.values())      # (no name seen twice)
     src = tmp_path / "sz.c"
-    src.write_text('#include "koaf.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(KoafGemm),sizeof(KoafOperand),offsetof(KoafGemm,C),offsetof(KoafGemm,stats),'
-                   'offsetof(KoafGemm,cmap),offsetof(KoafOperand,sc));return 0;}\n')
+    src.write_text('#include "koaf.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){\n'
+                   + "".join(f'printf("%zu\\n",(size_t){e});\n' for e in py) + "return 0;}\n")
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", str(ROOT / "include"), str(src), "-o", str(exe)], check=True)
-    c = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    py = [ctypes.sizeof(_lib.KoafGemm), ctypes.sizeof(_lib.KoafOperand), _lib.KoafGemm.C.offset,
-          _lib.KoafGemm.stats.offset, _lib.KoafGemm.cmap.offset, _lib.KoafOperand.sc.offset]
+    out = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    assert len(out) == len(py)
+    c = dict(zip(py, out))
     assert c == py
+    assert [c[f"sizeof({n})"] for n in structs] == [200, 728, 80, 56, 24, 32, 32, 24, 88]
+    assert [c["offsetof(KoafGemm,C)"], c["offsetof(KoafGemm,stats)"], c["offsetof(KoafGemm,cmap)"], c["offsetof(KoafOperand,sc)"]] == \
+        [_lib.KoafGemm.C.offset, _lib.KoafGemm.stats.offset, _lib.KoafGemm.cmap.offset, _lib.KoafOperand.sc.offset]
+
+
+def test_library_of_another_abi_version_is_refused(tmp_path, monkeypatch):
+    """lib() compares koaf_version() of what it loaded with KOAF_VERSION of the header it parsed, before it binds anything else"""
+    from oaprogressionmmf_amd import _lib
+    real = _lib.lib()
+    assert real.koaf_version() == _lib.defines()["KOAF_VERSION"] == 200
+    hdr, n = re.subn(r"(#define KOAF_VERSION) 200\b", r"\1 210", _lib.HEADER.read_text())
+    assert n == 1
+    (tmp_path / "koaf.h").write_text(hdr)
+    with monkeypatch.context() as mp:
+        mp.setattr(_lib, "HEADER", tmp_path / "koaf.h")
+        mp.setattr(_lib, "_LIB", None)
+        with pytest.raises(_lib.KoafError) as e:
+            _lib.lib()
+        msg = str(e.value)
+        assert "200" in msg and "210" in msg and "make -C" in msg and str(_lib.LIB_PATH) in msg
+        assert _lib._LIB is None
+    monkeypatch.setattr(_lib, "_LIB", None)                  # the real header again: the same file loads
+    assert _lib.lib() is not real and _lib.lib().koaf_version() == 200
+
+
+def test_constants_come_from_the_header():
+    from oaprogressionmmf_amd import _lib, ops
+    d = _lib.defines()
+    assert (d["KOAF_OK"], d["KOAF_EINVAL"], d["KOAF_ELAUNCH"]) == (0, -1, -2)
+    assert ops.ACT_SCALE == d["KOAF_ACT_SCALE"] == 16.0 and isinstance(ops.ACT_SCALE, float)
 
 
 def _cfgs():
@@ -161,6 +202,9 @@ def test_no_cpu_fallback_and_no_oracle_in_product():
     for f in (ROOT / "oaprogressionmmf_amd").rglob("*.py"):
         txt = f.read_text()
         assert "import oracle" not in txt and "from oracle" not in txt and "koafusion_cpu" not in txt, f
+        # one door to the library: only ops.py calls it (and _lib.py defines it)
+        if f.name not in ("ops.py", "_lib.py"):
+            assert "lib()" not in txt and not re.search(r"from\s+[\w.]*_lib\s+import[^\n]*\b(lib|check)\b", txt), f
 
 
 def test_checkpoint_roundtrip(tmp_path):
