@@ -202,6 +202,8 @@ __global__ void __launch_bounds__(768) wgrad3x3_ring_kernel(Wg3Params p) {
 }
 }  // namespace
 
+void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
+
 // k-ranges of the ring kernel for this layer: about four rounds of one block per CU (the weight gradients run on a low-priority
 // stream beside the critical path: blocks of ~0.5 ms give the CUs back often enough; 256 long blocks cost 15 ms per step), whole
 // multiples of 8 (an XCD each)
@@ -249,6 +251,13 @@ int koaf_wgrad3_ring(const uint16_t* dy_planes, const uint16_t* x_planes, float*
     const int groups = (p.nk + 7) / 8;
     const int D = (W + 2 + 1 + 31) >> 5;
     const dim3 grid((unsigned)(groups * 8 * ncomb));
+    {
+        // the launch record (koaf.h koaf_launch_log): the ring is no koaf_gemm, its entry says what it stands for as one
+        KoafGemm g{};
+        g.bm = g.bn = 64; g.fmt = 1;
+        g.M = Cout; g.N = 9 * Cin; g.K = (int)((int64_t)N * (H + 2) * (W + 2));
+        koaf_log_launch("koaf_wgrad3/ring", g, dim3((unsigned)ncomb, (unsigned)p.nk), dim3(grid.x, (unsigned)p.nk));
+    }
     if (2 * D + 3 <= 8) hipLaunchKernelGGL(wgrad3x3_ring_kernel<8>, grid, dim3(768), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(wgrad3x3_ring_kernel<16>, grid, dim3(768), 0, (hipStream_t)stream, p);
     int rc = koaf_check_launch("koaf_wgrad3_ring");

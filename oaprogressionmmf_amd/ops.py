@@ -210,8 +210,8 @@ def launch_log(on):
 
 def launch_log_read():
     """the launches recorded since launch_log(True): one dict per koaf_gemm launch, in launch order -- variant ("koaf_gemm",
-    "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"), bm, bn, tiles, grid_x (< tiles: persistent blocks walk), splitk,
-    nbatch, fmt, a_tf, b_tf, act16, M, N, K, emit"""
+    "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"; "koaf_wgrad3/ring": the 3x3 weight-gradient ring kernel, splitk = its
+    k-ranges), bm, bn, tiles, grid_x (< tiles: persistent blocks walk), splitk, nbatch, fmt, a_tf, b_tf, act16, M, N, K, emit"""
     L = lib()
     n = min(L.koaf_launch_log_read(None, 0), 4096)        # (launches seen; the record keeps the first 4096)
     buf = (KoafLaunchRec * max(n, 1))()
@@ -355,14 +355,24 @@ def _dy_planes(dy, dy_amax, npo, Cout):
     return act_planes(dy, npo, Cout, 0, amax=dy_amax)
 
 
-def conv2d_wgrad(dy, x, dw, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None, in_sh=None, dy_amax=None, aplanes=None):
+def _slab_ws(slabs, ws, like, what):
+    """the split-K slab workspace of `ws` floats: the caller's (fp32, on the device, at least that large) or a fresh one"""
+    if slabs is None:
+        return _empty((ws,), like) if ws > 0 else None
+    if not slabs.is_cuda or slabs.dtype != torch.float32 or not slabs.is_contiguous() or slabs.numel() < ws:
+        raise KoafError(f"{what}: the slab workspace is a contiguous fp32 device tensor of at least {ws} elements")
+    return slabs
+
+
+def conv2d_wgrad(dy, x, dw, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None, in_sh=None, dy_amax=None, aplanes=None,
+                 slabs=None):
     """writes dw (packed [Cout,KH,KW,Cin] memory); dy_amax (device scalar max |dy|): fp16 scheme; dy may be a BnApply.
     aplanes (None = gathered stride-1 kernels on the fp16 scheme): both operands from activation plane images (dy's are
-    shared with conv2d_dgrad), moved K-major by LDS-DMA."""
+    shared with conv2d_dgrad), moved K-major by LDS-DMA.
+    slabs (None = allocated here): the split-K workspace, at least koaf_conv2d_wgrad_ws floats."""
     L = lib()
     dyp, amp, app, like = _dy_args(dy, dy_amax)
-    ws = L.koaf_conv2d_wgrad_ws(N, H, W, Cin, Cout, KH, KW, stride, pad)
-    slabs = _empty((ws,), like) if ws > 0 else None
+    slabs = _slab_ws(slabs, L.koaf_conv2d_wgrad_ws(N, H, W, Cin, Cout, KH, KW, stride, pad), like, "conv2d_wgrad")
     if aplanes is None:
         aplanes = ((APLANES_MASK & 4) and KH * KW > 1 and stride == 1 and Cin % 8 == 0 and Cout % 8 == 0 and
                    (app is not None or dy_amax is not None))
@@ -432,10 +442,10 @@ def gconv3x3_dgrad(dy, wexp, N, H, W, C, stride):
     return dx
 
 
-def gconv3x3_wgrad(dy, x, N, H, W, C, stride, in_sc=None, in_sh=None):
+def gconv3x3_wgrad(dy, x, N, H, W, C, stride, in_sc=None, in_sh=None, slabs=None):
+    """slabs (None = allocated here): the split-K workspace, at least koaf_gconv3x3_wgrad_ws floats"""
     L = lib()
-    ws = L.koaf_gconv3x3_wgrad_ws(N, H, W, C, stride)
-    slabs = _empty((ws,), dy)
+    slabs = _slab_ws(slabs, L.koaf_gconv3x3_wgrad_ws(N, H, W, C, stride), dy, "gconv3x3_wgrad")
     dwexp = _empty((C // 64, 64, 9, 64), dy)
     e0 = _prof_begin()
     dam = getattr(dy, "_koaf_amax", None) if CONV_F16 else None
