@@ -281,7 +281,7 @@ typedef struct KoafBnApply {
  * mode, selected per model (config key `activation_storage: bf16`, default fp32), reported by bench.py as a named secondary
  * with its measured error against the fp32 mode; the parity gate (1e-3 of the reference) is the fp32 mode's.
  * Activation arguments per entry point: koaf_conv2d_fwd / koaf_gconv3x3_fwd x, y; koaf_conv2d_dgrad(_bnb) dy_apply->c and
- * bnb->c / y / c2; koaf_conv2d_wgrad / koaf_gconv3x3_wgrad x and dy_apply->c; koaf_stem_fwd y; koaf_colstats x; koaf_bn_add_relu /
+ * bnb->c / y / c2; koaf_conv2d_wgrad / koaf_gconv3x3_wgrad x and dy_apply->c; koaf_stem_fwd y; koaf_stem_wgrad / koaf_stem_dgrad dy_apply->c; koaf_colstats x; koaf_bn_add_relu /
  * koaf_bn_relu c, idt, y; koaf_bn_bwd_reduce c, ymask; koaf_bn_bwd_apply c; koaf_maxpool_fwd c, y; koaf_gap_fwd y; koaf_act_planes
  * x (tf 0 / 1) or x2 (tf 2). */
 
@@ -407,6 +407,15 @@ int koaf_stem_wgrad(const float* dy, const float* x, float* dw1t, int32_t N, int
 /* w [64,7,7,3] packed -> w1t [49][64] (sum over the 3 channels); gradient un-fold (copy x3) */
 int koaf_stem_fold_w(const float* w, float* w1t, void* stream);
 int koaf_stem_unfold_dw(const float* dw1t, float* dw, void* stream);
+/* Data gradient of the stem (input-gradient / saliency path; the train step's inputs are leaves and never call it):
+ *   dx[n][iy][ix] = sum over (kh, kw, co) with (iy+3-kh), (ix+3-kw) even and in range of
+ *                   dy[n][(iy+3-kh)/2][(ix+3-kw)/2][co] * w1t[kh*7+kw][co]
+ * dx [N,H,W]: the gradient of the single-channel image (the three repeated channels fold into one as in forward); every element
+ * is written.  Gather form -- a 16 x 16 tile of dy pixels forms its 49 tap sums with fp32 FMAs, the four input-pixel parity
+ * classes then collect their 3x3 / 3x4 / 4x3 / 4x4 windows through LDS in a fixed order: no atomics, run-to-run identical bits.
+ * dy_apply / act16: as for koaf_stem_wgrad (dy formed on load, never written). */
+int koaf_stem_dgrad(const float* dy, const float* w1t, float* dx, int32_t N, int32_t H, int32_t W,
+                    const KoafBnApply* dy_apply, int32_t act16, void* stream);
 
 /* ---- BatchNorm2d (nn.BatchNorm2d; _torchvision.py:172,121-131) ------------------------------- */
 /* per-block column sums / sums of squares of x [rows][C] -> part [*part_rows][2][C]
@@ -464,6 +473,14 @@ int koaf_bn_bwd_finalize(const float* part, int32_t part_rows, int32_t C, int64_
                          const float* sc, const float* invstd, float* dgamma, float* dbeta,
                          float* coef, int32_t nsum, int32_t i1, double* ws, const float* mean,
                          const float* dz_amax, float* amax, void* stream);
+/* The same finalisation for a BatchNorm in EVAL mode (running statistics: y = sc*c + sh with constant sc, sh), whose backward
+ * is dc = sc*dz: coef [coef_rows][C] = {sc, 0, 0[, 0]} (coef_rows 3 | 4: the layouts koaf_bn_bwd_apply / KoafBnApply read),
+ * dgamma / dbeta (nullable) the same sums as in train mode -- with xhat formed from the running statistics the reductions
+ * already used -- and amax (nullable, coef_rows 4) = max_c |sc| * *dz_amax.  part may be NULL when neither dgamma nor dbeta is
+ * wanted (frozen parameters): nothing is reduced then. */
+int koaf_bn_bwd_finalize_eval(const float* part, int32_t part_rows, int32_t C, const float* sc, float* dgamma, float* dbeta,
+                              float* coef, int32_t coef_rows, int32_t nsum, int32_t i1, double* ws, const float* dz_amax,
+                              float* amax, void* stream);
 /* dc = coef0*(dz - coef1) - coef2*(c - mean), materialised (consumers that are not GEMMs: the stem's weight gradient; GEMMs
  * without scale information).  amax (nullable): device scalar raised to max |dc| (atomic max; zero it beforehand). */
 int koaf_bn_bwd_apply(const float* dz, const float* c, const float* mean, const float* coef,
@@ -500,6 +517,13 @@ int koaf_gap_bwd(const float* dout, float* dy, int32_t N, int32_t HW, int32_t C,
 /* "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209-210): x [B,R,C,S] -> out [B*S,R,C] */
 int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,
                     void* stream);
+/* its transpose "(b s) r c -> b r c s": x [B*S,R,C] -> out [B,R,C,S] (the slice fold's backward) */
+int koaf_slice_unfold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,
+                      void* stream);
+/* out[b] = sum_i a[b][i] * b[b][i] over a, b [B][n] (gradient x input totals).  Two fixed-order stages, no atomics: run-to-run
+ * identical bits.  ws: B * koaf_rowdot_ws(n) floats. */
+int64_t koaf_rowdot_ws(int64_t n);
+int koaf_rowdot(const float* a, const float* b, int32_t B, int64_t n, float* out, float* ws, void* stream);
 /* F.interpolate(scale 0.5, align_corners=False, (bi|tri)linear) == 2x average pooling
  * (preproc/_pt.py:189-192).  x [B,R,C,S] -> out [B,R/2,C/2,S/fs], fs in {1,2}; S==1 for XR. */
 int koaf_downscale2(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,

@@ -385,6 +385,38 @@ __global__ void __launch_bounds__(1024) bn_bwd_finalize_kernel(const T* __restri
     if (amax && mean) block_amax_raise(bound, amax);
 }
 
+// eval-mode BatchNorm (y = sc*c + sh with constant coefficients): dc = sc*dz, so coef = {sc, 0, 0[, 0]}; dgamma / dbeta are
+// the sums the train-mode kernel above forms, added in the same order
+template <typename T>
+__global__ void __launch_bounds__(1024) bn_bwd_finalize_eval_kernel(const T* __restrict__ part, int rows, int C,
+                                                                    const float* __restrict__ sc, float* dgamma, float* dbeta,
+                                                                    float* coef, int coef_rows, int nsum, int i1,
+                                                                    const float* __restrict__ dz_amax, float* amax) {
+    __shared__ double red[2][16][64];
+    float bound = 0.f;
+    const int cx = threadIdx.x & 63, gy = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cx;
+    double a = 0.0, b = 0.0;
+    if (part && c < C)
+        for (int r = gy; r < rows; r += 16) {
+            a += (double)part[((int64_t)r * nsum + 0) * C + c];
+            b += (double)part[((int64_t)r * nsum + i1) * C + c];
+        }
+    red[0][gy][cx] = a;
+    red[1][gy][cx] = b;
+    __syncthreads();
+    if (gy == 0 && c < C) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int j = 0; j < 16; ++j) { s1 += red[0][j][cx]; s2 += red[1][j][cx]; }
+        if (dbeta) dbeta[c] = (float)s1;
+        if (dgamma) dgamma[c] = (float)s2;
+        coef[c] = sc[c];
+        for (int k = 1; k < coef_rows; ++k) coef[k * C + c] = 0.f;
+        if (amax) bound = fabsf(sc[c]) * (dz_amax ? *dz_amax : 0.f);
+    }
+    if (amax) block_amax_raise(bound, amax);
+}
+
 template <bool H>
 __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restrict__ dz, const float* __restrict__ c,
                                                            const float* __restrict__ mean,
@@ -613,6 +645,39 @@ __global__ void __launch_bounds__(256) gap_bwd_kernel(const float* __restrict__ 
         const int64_t n = i / ((int64_t)C4 * HW);
         *(v4f*)&dy[i * 4] = *(const v4f*)&dout[n * C + cv] * inv;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-sample dot product (gradient x input totals): out[b] = sum_i a[b][i] * b[b][i].  Stage 1: one block per RD_CHUNK elements,
+// fp64 accumulation (a product of two fp32 values is exact there), fixed lane / wave order; stage 2: one wave per sample adds
+// the block sums in index order.  No atomics: the bits do not depend on scheduling.
+// ------------------------------------------------------------------------------------------------
+constexpr int RD_CHUNK = 8192;
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ void __launch_bounds__(256) rowdot_part_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
+                                                          int nblk, double* __restrict__ ws) {
+    const int s = blockIdx.y;
+    const int64_t r0 = (int64_t)blockIdx.x * RD_CHUNK, r1 = r0 + RD_CHUNK < n ? r0 + RD_CHUNK : n;
+    const float* as = a + (int64_t)s * n;
+    const float* bs = b + (int64_t)s * n;
+    double acc = 0.0;
+    for (int64_t i = r0 + threadIdx.x; i < r1; i += 256) acc += (double)as[i] * (double)bs[i];
+    acc = wave_sum_d(acc);
+    __shared__ double red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) ws[(int64_t)s * nblk + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+__global__ void __launch_bounds__(64) rowdot_final_kernel(const double* __restrict__ ws, int nblk, float* __restrict__ out) {
+    const int s = blockIdx.x;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 64) acc += ws[(int64_t)s * nblk + i];
+    acc = wave_sum_d(acc);
+    if (threadIdx.x == 0) out[s] = (float)acc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1272,6 +1337,26 @@ extern "C" int koaf_bn_bwd_finalize(const float* part, int32_t part_rows, int32_
                            1.0 / (double)count, sc, invstd, dgamma, dbeta, coef, nsum, i1, mean, dz_amax, sq, amax);
     return koaf_check_launch("koaf_bn_bwd_finalize");
 }
+extern "C" int koaf_bn_bwd_finalize_eval(const float* part, int32_t part_rows, int32_t C, const float* sc, float* dgamma,
+                                         float* dbeta, float* coef, int32_t coef_rows, int32_t nsum, int32_t i1, double* ws,
+                                         const float* dz_amax, float* amax, void* stream) {
+    KOAF_REQUIRE(C > 0 && sc && coef && (coef_rows == 3 || coef_rows == 4), "koaf_bn_bwd_finalize_eval: bad args");
+    KOAF_REQUIRE(part ? part_rows > 0 : (!dgamma && !dbeta), "koaf_bn_bwd_finalize_eval: dgamma / dbeta need the partial sums");
+    KOAF_REQUIRE(!part || (nsum >= 2 && i1 >= 1 && i1 < nsum), "koaf_bn_bwd_finalize_eval: bad (nsum, i1)");
+    KOAF_REQUIRE(!amax || coef_rows == 4, "koaf_bn_bwd_finalize_eval: amax belongs to the four-row form");
+    if (amax && hipMemsetAsync(amax, 0, sizeof(float), STREAM) != hipSuccess) {
+        koaf_set_error("koaf_bn_bwd_finalize_eval: memset failed");
+        return KOAF_ELAUNCH;
+    }
+    const int S = part ? part_reduce(part, part_rows, C, nsum, i1, ws, STREAM) : 0;
+    if (S)
+        hipLaunchKernelGGL(bn_bwd_finalize_eval_kernel<double>, dim3((C + 63) / 64), dim3(1024), 0, STREAM, ws, S, C, sc, dgamma,
+                           dbeta, coef, coef_rows, 2, 1, dz_amax, amax);
+    else
+        hipLaunchKernelGGL(bn_bwd_finalize_eval_kernel<float>, dim3((C + 63) / 64), dim3(1024), 0, STREAM, part, part_rows, C, sc,
+                           dgamma, dbeta, coef, coef_rows, nsum, i1, dz_amax, amax);
+    return koaf_check_launch("koaf_bn_bwd_finalize_eval");
+}
 extern "C" int koaf_bn_bwd_apply(const float* dz, const float* c, const float* mean, const float* coef, float* dc,
                                  int64_t rows, int32_t C, float* amax, int32_t act16, void* stream) {
     KOAF_REQUIRE(dz && c && mean && coef && dc && rows > 0 && C % 4 == 0, "koaf_bn_bwd_apply: bad args");
@@ -1320,6 +1405,25 @@ extern "C" int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R,
     dim3 grid((P + 31) / 32, (S + 31) / 32, B);
     hipLaunchKernelGGL(slice_fold_kernel, grid, dim3(256), 0, STREAM, x, out, P, S);
     return koaf_check_launch("koaf_slice_fold");
+}
+// the transpose of the transpose: x [B][S][P] -> out [B][P][S], the same tile kernel with the two extents exchanged
+extern "C" int koaf_slice_unfold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S, void* stream) {
+    KOAF_REQUIRE(x && out && B > 0 && R > 0 && Cc > 0 && S > 0 && B <= 65535, "koaf_slice_unfold: bad args");
+    const int64_t P = (int64_t)R * Cc;
+    KOAF_REQUIRE(P <= 65535ll * 32, "koaf_slice_unfold: image too large");
+    dim3 grid((S + 31) / 32, (unsigned)((P + 31) / 32), B);
+    hipLaunchKernelGGL(slice_fold_kernel, grid, dim3(256), 0, STREAM, x, out, S, (int)P);
+    return koaf_check_launch("koaf_slice_unfold");
+}
+extern "C" int64_t koaf_rowdot_ws(int64_t n) { return n > 0 ? 2 * cdiv64(n, RD_CHUNK) : 0; }      // (fp64 block sums)
+extern "C" int koaf_rowdot(const float* a, const float* b, int32_t B, int64_t n, float* out, float* ws, void* stream) {
+    KOAF_REQUIRE(a && b && out && ws && B > 0 && B <= 65535 && n > 0, "koaf_rowdot: bad args");
+    KOAF_REQUIRE((((uintptr_t)ws) & 7) == 0, "koaf_rowdot: the workspace is 8-byte aligned");
+    const int64_t nblk = cdiv64(n, RD_CHUNK);
+    KOAF_REQUIRE(nblk < (1ll << 31), "koaf_rowdot: rows too long");
+    hipLaunchKernelGGL(rowdot_part_kernel, dim3((unsigned)nblk, B), dim3(256), 0, STREAM, a, b, n, (int)nblk, (double*)ws);
+    hipLaunchKernelGGL(rowdot_final_kernel, dim3(B), dim3(64), 0, STREAM, (const double*)ws, (int)nblk, out);
+    return koaf_check_launch("koaf_rowdot");
 }
 extern "C" int koaf_downscale2(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S, int32_t fs,
                                void* stream) {

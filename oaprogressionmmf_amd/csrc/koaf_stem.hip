@@ -472,3 +472,117 @@ int koaf_stem_wgrad_mma(const float* dy, const float* x, float* slabs, int nb, i
         hipLaunchKernelGGL((stem_wgrad_mma_kernel<false, false>), grid, dim3(256), 0, st, dy, x, slabs, N, H, W, OH, OW, nullptr, nullptr);
     return koaf_check_launch("koaf_stem_wgrad/mma");
 }
+
+// ================================================================================================
+// Stem data gradient (koaf.h koaf_stem_dgrad):  dx[iy][ix] = sum_{kh, kw, co} dc[(iy+3-kh)/2][(ix+3-kw)/2][co] * w1t[kh*7+kw][co]
+// over the taps whose (iy+3-kh), (ix+3-kw) are even.  By input-pixel parity these are four stride-1 walks over the dc grid: an
+// even row takes kh = 1, 3, 5 (dc rows a+1, a, a-1 for iy = 2a), an odd row kh = 0, 2, 4, 6 (a+2 .. a-1), columns alike -- tap
+// windows of 3x3, 3x4, 4x3 and 4x4, the split stem_wgrad_mma_kernel makes of x.  In two phases per 16 x 16 tile of dc pixels:
+//   * contraction: one thread per dc pixel forms all 49 tap sums  t[tap] = sum_co dc[co] * w1t[tap][co]  with fp32 FMAs -- the
+//     weight index is the same for every lane, so the weights arrive through the scalar cache as scalar operands of the (packed)
+//     FMAs and the 49 sums stay in registers: no LDS traffic in the contraction.  dc is read as given or formed on load from (dz, c, coef)
+//     (KoafBnApply, the arithmetic of the weight gradient's loader); pixels outside the dc grid contribute zero;
+//   * collection: t goes to LDS as [pixel][49] (odd stride: conflict-free) and every input pixel of the tile's 26 x 26 interior
+//     (13 x 13 dc pixels; one halo row / column before, two behind) adds its window's entries in a fixed order.
+// No atomics anywhere: the bits do not depend on scheduling.  The halo costs (16 / 13)^2 = 1.5 x the 12.25 * 64 FMAs per input
+// pixel the sum needs; the kernel only runs on the input-gradient (saliency) path.
+// ================================================================================================
+namespace {
+constexpr int SD_T = 16;                 // dc pixels per tile side (one thread each)
+constexpr int SD_I = SD_T - 3;           // dc pixels per side whose 2 x 2 input pixels the tile completes
+constexpr int SD_O = 2 * SD_I;           // input pixels per tile side
+
+template <bool APPLY, bool C16>
+__global__ void __launch_bounds__(256) stem_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w1t,
+                                                         float* __restrict__ dx, int H, int W, int OH, int OW, int tyn, int txn,
+                                                         const float* __restrict__ cc, const float* __restrict__ coef) {
+    __shared__ float tp[SD_T * SD_T * 49];
+    const int t = threadIdx.x;
+    int b = blockIdx.x;
+    const int txi = b % txn;
+    b /= txn;
+    const int tyi = b % tyn, n = b / tyn;
+    const int a0 = tyi * SD_I, b0 = txi * SD_I;                   // first interior dc pixel of the tile
+    const int py = t >> 4, px = t & 15;
+    const int oy = a0 - 1 + py, ox = b0 - 1 + px;
+    float acc[49];
+#pragma unroll
+    for (int k = 0; k < 49; ++k) acc[k] = 0.f;
+    if ((unsigned)oy < (unsigned)OH && (unsigned)ox < (unsigned)OW) {
+        const int64_t base = (((int64_t)n * OH + oy) * OW + ox) * 64;
+#pragma unroll 1
+        for (int h = 0; h < 2; ++h) {
+            // 32 channels a turn, all of their loads issued before the first is used: a lane reads its pixel's 256-byte row, so a
+            // wave's load instruction touches 64 rows, and the bytes in flight (not the FMAs) set the pace with fewer outstanding
+            v4f d[8], cv[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int co = 32 * h + 4 * q;
+                d[q] = *(const v4f*)(dy + base + co);
+                if constexpr (APPLY) {
+                    if constexpr (C16) {
+                        const uint2 raw = *(const uint2*)(reinterpret_cast<const unsigned short*>(cc) + base + co);
+                        cv[q] = widen_bf16x4(raw.x, raw.y);
+                    } else cv[q] = *(const v4f*)(cc + base + co);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int co = 32 * h + 4 * q;
+                if constexpr (APPLY) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) d[q][j] = fmaf(coef[co + j], d[q][j], fmaf(-coef[128 + co + j], cv[q][j], coef[192 + co + j]));
+                }
+                // (the group's weight offset passes through a scalar move the compiler cannot see through: otherwise it merges the
+                // loads of one tap across the eight groups into 16-dword loads that live through all of them, and the scalar
+                // registers spill)
+                int cw;
+                asm volatile("s_mov_b32 %0, %1" : "=s"(cw) : "s"(co));
+                const float* wq = w1t + cw;
+#pragma unroll
+                for (int k = 0; k < 49; ++k)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[k] = fmaf(d[q][j], wq[k * 64 + j], acc[k]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 49; ++k) tp[t * 49 + k] = acc[k];
+    __syncthreads();
+    for (int i = t; i < SD_O * SD_O; i += 256) {
+        const int ly = i / SD_O, lx = i - ly * SD_O;
+        const int iy = 2 * a0 + ly, ix = 2 * b0 + lx;
+        if (iy >= H || ix >= W) continue;
+        float s = 0.f;
+        for (int kh = 1 - (ly & 1); kh < 7; kh += 2) {            // dc row a0 + (ly + 3 - kh) / 2 = tile row qy
+            const int qy = ((ly + 3 - kh) >> 1) + 1;
+            for (int kw = 1 - (lx & 1); kw < 7; kw += 2) {
+                const int qx = ((lx + 3 - kw) >> 1) + 1;
+                s += tp[(qy * SD_T + qx) * 49 + kh * 7 + kw];
+            }
+        }
+        dx[((int64_t)n * H + iy) * W + ix] = s;
+    }
+}
+}  // namespace
+
+extern "C" int koaf_stem_dgrad(const float* dy, const float* w1t, float* dx, int32_t N, int32_t H, int32_t W,
+                               const KoafBnApply* dy_apply, int32_t act16, void* stream) {
+    KOAF_REQUIRE((dy || dy_apply) && w1t && dx && N > 0 && H > 0 && W > 0, "koaf_stem_dgrad: bad args");
+    KOAF_REQUIRE(!dy_apply || (dy_apply->dz && dy_apply->c && dy_apply->coef), "koaf_stem_dgrad: dy_apply needs dz / c / coef");
+    const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
+    const int tyn = (OH + SD_I - 1) / SD_I, txn = (OW + SD_I - 1) / SD_I;
+    const int64_t blocks = (int64_t)N * tyn * txn;
+    KOAF_REQUIRE(blocks < (1ll << 31), "koaf_stem_dgrad: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)blocks);
+    if (dy_apply) {
+        if (act16) hipLaunchKernelGGL((stem_dgrad_kernel<true, true>), grid, dim3(256), 0, st, dy_apply->dz, w1t, dx, H, W, OH, OW, tyn, txn,
+                                      dy_apply->c, dy_apply->coef);
+        else hipLaunchKernelGGL((stem_dgrad_kernel<true, false>), grid, dim3(256), 0, st, dy_apply->dz, w1t, dx, H, W, OH, OW, tyn, txn,
+                                dy_apply->c, dy_apply->coef);
+    } else
+        hipLaunchKernelGGL((stem_dgrad_kernel<false, false>), grid, dim3(256), 0, st, dy, w1t, dx, H, W, OH, OW, tyn, txn, nullptr, nullptr);
+    return koaf_check_launch("koaf_stem_dgrad");
+}

@@ -119,11 +119,14 @@ class LayerNormFn(torch.autograd.Function):
         if not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         w, b = ctx.weight, ctx.bias
-        gw, accw = grad_target(w)
-        gb, accb = grad_target(b)
+        # (a frozen parameter's sums go to a scratch vector the kernel still writes, and are not delivered)
+        gw, accw = grad_target(w) if w.requires_grad else (torch.empty_like(w), False)
+        gb, accb = grad_target(b) if b.requires_grad else (torch.empty_like(b), False)
         dx = ops.layernorm_bwd(dy2, x2, w.detach(), mean, rstd, gw, gb, rows, D)
-        deliver_grad(w, gw, accw)
-        deliver_grad(b, gb, accb)
+        if w.requires_grad:
+            deliver_grad(w, gw, accw)
+        if b.requires_grad:
+            deliver_grad(b, gb, accb)
         ctx.saved = None
         return dx.view(ctx.xshape), None, None, None
 

@@ -51,6 +51,20 @@ def mr_view(config):
     return "src" if lay == "ncdhw" else "rc"
 
 
+class _SliceFoldFn(torch.autograd.Function):
+    """the "rc" slice fold with its backward (koaf_slice_unfold), for volumes that ask for a gradient (saliency maps)"""
+
+    @staticmethod
+    def forward(ctx, x, B, R, C, S):
+        ctx.dims = (B, R, C, S)
+        return ops.slice_fold(x, B, R, C, S)
+
+    @staticmethod
+    def backward(ctx, g):
+        B, R, C, S = ctx.dims
+        return ops.slice_unfold(g.contiguous(), B, R, C, S).view(B, 1, R, C, S), None, None, None, None
+
+
 def fold_slices(x, dims_view="rc"):
     """(B,1,R,C,S) -> single-channel image batch for the 2-D trunk (the 1->3 repeat is folded into conv1).
     rc: "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209); cs / rs: _mrN_cnn_trf.py:112-117; src: the same slices as rc
@@ -65,6 +79,8 @@ def fold_slices(x, dims_view="rc"):
         raise ValueError("koafusion volumes are single-channel")
     x = x.contiguous()
     if dims_view == "rc":
+        if x.requires_grad and torch.is_grad_enabled():
+            return _SliceFoldFn.apply(x, B, R, C, S).view(B * S, 1, R, C)
         return ops.slice_fold(x, B, R, C, S).view(B * S, 1, R, C)
     if dims_view == "cs":
         return x.view(B * R, 1, C, S)

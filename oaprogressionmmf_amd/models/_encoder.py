@@ -228,7 +228,10 @@ def _conv_bwd(conv, dc, x, N, H, W, in_saved, wexp, residual=None, need_dx=True,
         #                                                the fp16 scheme of both kinds of consumer)
     amax = getattr(dc, "_koaf_amax", None)
     sc, sh = (in_saved[2], in_saved[3]) if in_saved is not None else (None, None)
-    gw, acc = grad_target(conv.weight)
+    need_dw = conv.weight.requires_grad        # (a frozen weight: no weight gradient is formed, p.grad stays as it is)
+    gw, acc = grad_target(conv.weight) if need_dw else (None, False)
+    if not need_dw:
+        side = None
 
     def wgrad():
         if g == 1:
@@ -236,7 +239,7 @@ def _conv_bwd(conv, dc, x, N, H, W, in_saved, wexp, residual=None, need_dx=True,
         else:
             dwexp = ops.gconv3x3_wgrad(dc, x, N, H, W, cin, s, sc, sh)
             ops.gconv_compress_dw(dwexp, gw, cin, g)
-    if side is None:
+    if side is None and need_dw:
         wgrad()
         deliver_grad(conv.weight, gw, acc)
     early = side is not None and WGRAD_EARLY and need_dx and g == 1 and k == 1
@@ -260,36 +263,52 @@ def _conv_bwd(conv, dc, x, N, H, W, in_saved, wexp, residual=None, need_dx=True,
     return dx
 
 
+def _bn_train(bn):
+    """did this BatchNorm normalise with batch statistics (_bn_fin's rule)?  Otherwise its backward is the eval-mode one:
+    dc = sc*dz, the coefficients being constants (ops.bn_bwd train=False)"""
+    return bn.training or bn.running_mean is None
+
+
+def _bn_grad_targets(bn):
+    """((dgamma buffer, accumulate?), (dbeta buffer, accumulate?)); (None, False) for a frozen parameter: its sum is not formed"""
+    return (grad_target(bn.weight) if bn.weight.requires_grad else (None, False),
+            grad_target(bn.bias) if bn.bias.requires_grad else (None, False))
+
+
+def _bn_deliver(bn, gg, ag, gb, ab):
+    if gg is not None:
+        deliver_grad(bn.weight, gg, ag)
+    if gb is not None:
+        deliver_grad(bn.bias, gb, ab)
+
+
 def _bn_bwd(bn, g, c, saved, rows, mask_mode, ymask=None, dz_out=None, dc_out=None, fused=None, pool=None):
     """-> dc of a BatchNorm(+ReLU mask): an ops.BnApply when the consumers can form it on load (fused), else the tensor"""
     C = bn.num_features
-    gg, ag = grad_target(bn.weight)
-    gb, ab = grad_target(bn.bias)
+    (gg, ag), (gb, ab) = _bn_grad_targets(bn)
+    train = _bn_train(bn)
     if fused is None:
         fused = ops.CONV_F16
-        dc = ops.bn_bwd(g, c, saved, rows, C, rows, gg, gb, mask_mode, ymask=ymask, dz_out=dz_out, fused=fused)
+        dc = ops.bn_bwd(g, c, saved, rows, C, rows, gg, gb, mask_mode, ymask=ymask, dz_out=dz_out, fused=fused, train=train)
         if fused and not FUSE_APPLY:
             dc = dc.materialize(out=dc_out, want_amax=True)      # (A/B switch: dc written out, with its exact max |dc|)
     else:
         dc = ops.bn_bwd(g, c, saved, rows, C, rows, gg, gb, mask_mode, ymask=ymask, dz_out=dz_out,
-                        dc_out=None if fused else dc_out, fused=fused, pool=pool)
-    deliver_grad(bn.weight, gg, ag)
-    deliver_grad(bn.bias, gb, ab)
+                        dc_out=None if fused else dc_out, fused=fused, pool=pool, train=train)
+    _bn_deliver(bn, gg, ag, gb, ab)
     return dc
 
 
 def _bn_bwd_part(bn, part, nsum, i1, dz, c, saved, rows, dc_out=None, dzmax=None):
     """BatchNorm backward whose reduction was fused into the producing dgrad's epilogue (dzmax: the max |dz| it left)."""
     C = bn.num_features
-    gg, ag = grad_target(bn.weight)
-    gb, ab = grad_target(bn.bias)
+    (gg, ag), (gb, ab) = _bn_grad_targets(bn)
     fused = ops.CONV_F16 and dzmax is not None
     dc = ops.bn_bwd_from_part(part, nsum, i1, dz, c, saved, rows, C, rows, gg, gb, dc_out=None if fused else dc_out,
-                              fused=fused, dzmax=dzmax)
+                              fused=fused, dzmax=dzmax, train=_bn_train(bn))
     if fused and not FUSE_APPLY:
         dc = dc.materialize(out=dc_out, want_amax=True)
-    deliver_grad(bn.weight, gg, ag)
-    deliver_grad(bn.bias, gb, ab)
+    _bn_deliver(bn, gg, ag, gb, ab)
     return dc
 
 
@@ -436,6 +455,7 @@ class EncoderFn(torch.autograd.Function):
             N, _, H, W = x.shape
         else:
             N, H, W = x.shape
+        xshape = x.shape
         x = x.contiguous()
         conv1, bn1 = st["conv1"], st["bn1"]
         train = bn1.training
@@ -491,7 +511,7 @@ class EncoderFn(torch.autograd.Function):
                 c0 = None          # the stem output is rebuilt in backward too (one cheap 7x7 conv; 64 x H/2 x W/2 floats)
             ctx.state = dict(x=x, c0=c0, s0=s0, am=am, stages=stages_saved, any_recompute=bool(rset), caller=CALLER_STREAM,
                              block_level=block_level, adt=adt,
-                             dims=(N, H, W, H1, W1), last=(Hc, Wc, C), st=st, lane=lane, train=train)
+                             dims=(N, H, W, H1, W1), last=(Hc, Wc, C), st=st, lane=lane, train=train, xshape=xshape)
         return out
 
     @staticmethod
@@ -499,8 +519,9 @@ class EncoderFn(torch.autograd.Function):
         S = ctx.state
         ctx.state = None
         lane = S["lane"]
+        need_dx = ctx.needs_input_grad[0]
         if lane is None:
-            return EncoderFn._backward_body(S, gout, None)
+            return EncoderFn._backward_body(S, gout, None, need_dx)
         # multi-stream: this encoder's backward runs on its own lane (autograd already switched to the forward
         # stream and ordered it after the producer of gout); the caller's stream joins at the end of backward()
         main_s, side_s = lane_streams(gout.device, lane)
@@ -509,7 +530,11 @@ class EncoderFn(torch.autograd.Function):
             main_s.wait_stream(cur)
             gout.record_stream(main_s)
         with torch.cuda.stream(main_s):
-            out = EncoderFn._backward_body(S, gout, side_s)
+            out = EncoderFn._backward_body(S, gout, side_s, need_dx)
+        if out[0] is not None and cur != main_s:
+            # the input gradient was produced on the lane: the stream autograd hands it on from is ordered behind it
+            cur.wait_stream(main_s)
+            out[0].record_stream(cur)
         _register_join(main_s, S.get("caller"))
         return out
 
@@ -592,7 +617,7 @@ class EncoderFn(torch.autograd.Function):
         return dy
 
     @staticmethod
-    def _backward_body(S, gout, side_stream):
+    def _backward_body(S, gout, side_stream, need_dx=False):
         st = S["st"]
         N, H, W, H1, W1 = S["dims"]
         Hc, Wc, C = S["last"]
@@ -648,12 +673,19 @@ class EncoderFn(torch.autograd.Function):
             dy = EncoderFn._blocks_bwd(recs, dy, side)
             del recs, y
             next_in = stage_in
-        # stem: max-pool, BN0, conv1 weight gradient (no data gradient: the input is a leaf)
+        # stem: max-pool, BN0, conv1 weight gradient; the data gradient only when the input asks for one (saliency maps: in the
+        # train step the input is a leaf that does not)
         next_in = None
         conv1, bn1 = st["conv1"], st["bn1"]
+        need_dw = conv1.weight.requires_grad
+        if not (need_dx or need_dw or bn1.weight.requires_grad or bn1.bias.requires_grad):
+            if side is not None:
+                side.join()
+            return None, None, None, None, None
         c0 = S["c0"]
+        w1t = ops.stem_fold_w(packed_weight(conv1.weight)) if (c0 is None or need_dx) else None
         if c0 is None:
-            c0 = ops.stem_fwd(S["x"], ops.stem_fold_w(packed_weight(conv1.weight)), N, H, W, dtype=S["adt"])
+            c0 = ops.stem_fwd(S["x"], w1t, N, H, W, dtype=S["adt"])
         if FUSE_STEM_BWD:
             # the max-pool's input gradient is gathered inside the BatchNorm reduction and dc0 is formed by the weight gradient
             # while it loads (dz, c0): neither tensor is written (two of the four passes over the largest activation of the trunk)
@@ -661,12 +693,14 @@ class EncoderFn(torch.autograd.Function):
         else:
             da0 = ops.maxpool_bwd(dy, S["am"], N, H1, W1, 64)
             dc0 = _bn_bwd(bn1, da0, c0, S["s0"], N * H1 * W1, 2, dc_out=da0, fused=False)
-        gw, acc = grad_target(conv1.weight)
-        ops.stem_wgrad(dc0, S["x"], gw, N, H, W)
-        deliver_grad(conv1.weight, gw, acc)
+        if need_dw:
+            gw, acc = grad_target(conv1.weight)
+            ops.stem_wgrad(dc0, S["x"], gw, N, H, W)
+            deliver_grad(conv1.weight, gw, acc)
+        dx = ops.stem_dgrad(dc0, w1t, N, H, W).view(S["xshape"]) if need_dx else None     # (reads the same (dz, c0) as the weight gradient)
         if side is not None:
             side.join()
-        return None, None, None, None, None
+        return dx, None, None, None, None
 
 
 class KoafTrunk(nn.Sequential):
@@ -711,5 +745,5 @@ class KoafTrunk(nn.Sequential):
         lay = self._koaf_layout()
         anchor = lay["conv1"].weight
         # autograd runs Function.forward with grad mode off, so decide here whether backward can happen
-        keep = torch.is_grad_enabled() and anchor.requires_grad
+        keep = torch.is_grad_enabled() and (anchor.requires_grad or x.requires_grad)
         return EncoderFn.apply(x, self, anchor, keep, lane)

@@ -486,6 +486,15 @@ def stem_wgrad(dy, x, dw, N, H, W):
     return dw
 
 
+def stem_dgrad(dy, w1t, N, H, W):
+    """dx [N,H,W] = the stem's data gradient w.r.t. the single-channel image (koaf_stem_dgrad: gather form, no atomics); dy
+    [N,OH,OW,64] or a BnApply (the stem BatchNorm's backward, formed on load); w1t the folded weight of stem_fold_w"""
+    dyp, _, app, like = _dy_args(dy, None)
+    dx = _empty((N, H, W), like)
+    check(lib().koaf_stem_dgrad(dyp, _ptr(w1t), _ptr(dx), N, H, W, app, _a16(dy.c) if app is not None else 0, _stream()), "stem_dgrad")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------
 # batch norm
 # ------------------------------------------------------------------------------------------------
@@ -525,10 +534,13 @@ def bn_add_relu(c, saved, rows, C, idt=None, idsaved=None, out=None):
     return y
 
 
-def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz_out=None, dc_out=None, fused=False, pool=None):
+def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz_out=None, dc_out=None, fused=False, pool=None,
+           train=True):
     """Full BatchNorm(+ReLU mask) backward: reduce -> finalize -> dc.  g is the upstream gradient; with a mask the masked
     gradient dz is written to dz_out (default: in place over g).  fused=False: dc is written out (koaf_bn_bwd_apply) and
-    returned; fused=True: returns a BnApply -- the recipe of dc for the GEMM loaders -- and nothing is written."""
+    returned; fused=True: returns a BnApply -- the recipe of dc for the GEMM loaders -- and nothing is written.
+    train=False: the BatchNorm ran on its running statistics (`saved` holds them), so dc = sc*dz (koaf_bn_bwd_finalize_eval);
+    dgamma / dbeta may be None (frozen parameters): they are then not written."""
     L = lib()
     if pool is not None:
         # g is the gradient of the max-pool behind this BatchNorm(+ReLU): pool = (pool_g [N,OH,OW,C], argmax, N, H, W); the pool's
@@ -542,7 +554,7 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
         check(L.koaf_bn_bwd_reduce_pool(_ptr(pg), _ptr(am), _ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(saved[0]), _ptr(saved[1]),
                                         _ptr(dz), _ptr(part), ctypes.addressof(r), pN, pH, pW, C, _ptr(dzmax), _a16(c), _stream()),
               "bn_bwd_reduce_pool")
-        return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax)
+        return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
     if mask_mode != 0 and dz_out is None:
         dz_out = g  # mask in place
     part = _empty((L.koaf_colpart_rows(rows, C), 2, C), g)
@@ -552,16 +564,24 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
                                _ptr(saved[1]), mask_mode, _ptr(dz_out), _ptr(part), ctypes.addressof(r), rows, C,
                                _ptr(dzmax), _a16(c), _stream()), "bn_bwd_reduce")
     dz = dz_out if dz_out is not None else g
-    return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax)
+    return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
 
 
-def _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax):
+def _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train=True):
     L = lib()
     coef = _empty((4 if fused else 3, C), dz)
     amax = _empty((1,), dz) if fused else None
-    check(L.koaf_bn_bwd_finalize(_ptr(part), part.shape[0], C, count, _ptr(saved[2]), _ptr(saved[1]), _ptr(dgamma),
-                                 _ptr(dbeta), _ptr(coef), nsum, i1, _ptr(_reduce_ws(part.shape[0], C, dz)),
-                                 _ptr(saved[0]) if fused else None, _ptr(dzmax), _ptr(amax), _stream()), "bn_bwd_finalize")
+    if train:
+        check(L.koaf_bn_bwd_finalize(_ptr(part), part.shape[0], C, count, _ptr(saved[2]), _ptr(saved[1]), _ptr(dgamma),
+                                     _ptr(dbeta), _ptr(coef), nsum, i1, _ptr(_reduce_ws(part.shape[0], C, dz)),
+                                     _ptr(saved[0]) if fused else None, _ptr(dzmax), _ptr(amax), _stream()), "bn_bwd_finalize")
+    else:
+        # eval mode: dc = sc*dz; the partial sums only feed dgamma / dbeta and are left alone when neither is wanted
+        want = dgamma is not None or dbeta is not None
+        check(L.koaf_bn_bwd_finalize_eval(_ptr(part) if want else None, part.shape[0] if want else 0, C, _ptr(saved[2]), _ptr(dgamma),
+                                          _ptr(dbeta), _ptr(coef), 4 if fused else 3, nsum, i1,
+                                          _ptr(_reduce_ws(part.shape[0], C, dz)) if want else None, _ptr(dzmax), _ptr(amax),
+                                          _stream()), "bn_bwd_finalize_eval")
     if fused:
         return BnApply(dz, c, coef, amax, saved[0], rows, C)
     dc = dc_out if dc_out is not None else torch.empty(c.shape, device=c.device, dtype=torch.float32)
@@ -570,12 +590,12 @@ def _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc
     return dc
 
 
-def bn_bwd_from_part(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out=None, fused=False, dzmax=None):
+def bn_bwd_from_part(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out=None, fused=False, dzmax=None, train=True):
     """BatchNorm backward when the reduction already happened in a dgrad epilogue: finalize (+ apply unless fused; fused
-    needs dzmax, the device scalar max |dz| that epilogue left)."""
+    needs dzmax, the device scalar max |dz| that epilogue left); train=False: the eval-mode backward, see bn_bwd."""
     if fused and dzmax is None:
         raise KoafError("bn_bwd_from_part(fused=True) needs dzmax (conv2d_dgrad with bnb['dz_amax'])")
-    return _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax)
+    return _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
 
 
 def maxpool_fwd(c, saved, N, H, W, C):
@@ -611,6 +631,26 @@ def gap_bwd(dout, N, HW, C):
 def slice_fold(x, B, R, Cc, S):
     out = _empty((B * S, R, Cc), x)
     check(lib().koaf_slice_fold(_ptr(x), _ptr(out), B, R, Cc, S, _stream()), "slice_fold")
+    return out
+
+
+def slice_unfold(g, B, R, Cc, S):
+    """"(b s) r c -> b r c s": g [B*S,R,C] -> [B,R,C,S], the transpose of slice_fold (its backward)"""
+    out = _empty((B, R, Cc, S), g)
+    check(lib().koaf_slice_unfold(_ptr(g), _ptr(out), B, R, Cc, S, _stream()), "slice_unfold")
+    return out
+
+
+def rowdot(a, b):
+    """per-sample sum(a * b) of two contiguous fp32 tensors of one shape (B, ...) -> [B] (koaf_rowdot: fixed-order, no atomics)"""
+    if tuple(a.shape) != tuple(b.shape) or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise KoafError(f"rowdot: two fp32 tensors of one shape, got {tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    a, b = a.contiguous(), b.contiguous()
+    B = int(a.shape[0])
+    n = a.numel() // B
+    out = _empty((B,), a)
+    ws = torch.empty(B * lib().koaf_rowdot_ws(n) // 2, device=a.device, dtype=torch.float64)      # (the fp64 block sums)
+    check(lib().koaf_rowdot(_ptr(a), _ptr(b), B, n, _ptr(out), _ptr(ws), _stream()), "rowdot")
     return out
 
 

@@ -3,8 +3,9 @@ path.  The drivers themselves (hydra, data loaders, tensorboard, metrics) stay t
 from ._steps import downscale_inputs, train_epoch, train_step, predict_batch
 from ._eval import eval_epoch, ensemble_eval_foldw, InferenceTimer
 from ._graph import GraphedPredictor, GraphedTrainStep
-from ._explain import explain_epoch, ensemble_explain_foldw, modal_ablation, ablation_percent
+from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ablation_percent, input_gradients,
+                       saliency_maps)
 
 __all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
-           "ablation_percent"]
+           "ablation_percent", "input_gradients", "saliency_maps"]

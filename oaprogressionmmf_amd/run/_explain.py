@@ -5,12 +5,18 @@ baselines (= zeros) and one perturbation per evaluation; for that call captum's 
     attr[b, m] = f(x)[b, target_b] - f(x with modality m zeroed)[b, target_b]
 
 replicated over every element of input m (so the reference's mean over elements returns the difference itself).
-Here the M + 1 forwards run on the HIP path and only the (B, M) differences leave the device."""
+Here the M + 1 forwards run on the HIP path and only the (B, M) differences leave the device.
+
+Not in the reference: input gradients.  input_gradients / saliency_maps return d logit[b, target_b] / d x_m for every input
+(one forward and one backward through the HIP path, the trunks' data gradient down to the image included), and
+explain_epoch(explain_fn="input_x_grad") accumulates the per-modality totals sum(x_m * grad_m) -- the first-order estimate of
+what the ablation measures with M + 1 forwards."""
 from collections import defaultdict
 
 import numpy as np
 import torch
 
+from .. import ops
 from ._eval import _extract_modal
 from ._steps import downscale_inputs
 
@@ -35,6 +41,50 @@ def modal_ablation(model, xs, target):
     return torch.cat(cols, dim=1)
 
 
+def _targets(target, xs):
+    tgt = torch.as_tensor(target).to(xs[0].device).long().reshape(-1, 1)
+    if tgt.shape[0] == 1 and xs[0].shape[0] > 1:                   # a squeezed single target applies to every row
+        tgt = tgt.expand(xs[0].shape[0], 1)
+    return tgt
+
+
+def input_gradients(model, xs, target):
+    """tuple shaped like `xs` of d logit[b, target_b] / d x_m (fp32 device tensors), in whatever mode the model is in
+    (explanations: eval()).  The gradients are with respect to what the model receives.  Parameters are frozen for the call:
+    no weight gradient is formed and no p.grad is touched."""
+    tgt = _targets(target, xs)
+    leaves = tuple(x.detach().requires_grad_(True) for x in xs)
+    params = [p for p in model.parameters() if p.requires_grad]
+    for p in params:
+        p.requires_grad_(False)
+    try:
+        with torch.enable_grad():
+            sel = _forward_main(model, leaves).gather(1, tgt).sum()
+            grads = torch.autograd.grad(sel, leaves)
+    finally:
+        for p in params:
+            p.requires_grad_(True)
+    return tuple(g.detach() for g in grads)
+
+
+SALIENCY_KINDS = ("grad", "input_x_grad")
+
+
+def saliency_maps(model, xs, target, kind="grad"):
+    """per input, the gradient map ("grad") or gradient x input ("input_x_grad"), shaped like the input"""
+    if kind not in SALIENCY_KINDS:
+        raise ValueError(f"Unknown saliency kind: {kind}")
+    grads = input_gradients(model, xs, target)
+    if kind == "grad":
+        return grads
+    return tuple(x.detach() * g for x, g in zip(xs, grads))
+
+
+def input_x_grad_totals(xs, grads):
+    """(B, M) fp32 device tensor of sum(x_m * grad_m) per sample and modality (koaf_rowdot: fixed summation order)"""
+    return torch.stack([ops.rowdot(x.detach().float(), g) for x, g in zip(xs, grads)], dim=1)
+
+
 def ablation_percent(attrs):
     """eval_prog_fus.py:456-459: rows normalised to unit L1, absolute value, per cent rounded to 3 decimals
     (fp32 arithmetic on the CPU copy, as there)."""
@@ -43,11 +93,16 @@ def ablation_percent(attrs):
     return np.round(np.abs(t.numpy()) * 100., decimals=3)
 
 
-def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl"):
+def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None):
     """One pass of an eval()-mode model over `loader`; returns the reference's accumulator dict: exam_knee_id,
-    target, modal_names, modal_abl_attrs, modal_abl_percent (python lists, loader order)."""
-    if explain_fn != "modal_abl":
+    target, modal_names, modal_abl_attrs, modal_abl_percent (python lists, loader order).
+    explain_fn="input_x_grad" (not in the reference): the same dict with ixg_attrs = sum(x_m * grad_m) per modality and
+    ixg_percent (ablation_percent of those) instead, for one forward and one backward per batch.  The gradient x input maps
+    themselves (device tensors shaped like the inputs the model receives, i.e. after `downscale`) go to
+    sink(exam_knee_ids, modals, maps) when a sink is given, and never into the returned lists."""
+    if explain_fn not in ("modal_abl", "input_x_grad"):
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
+    field = "modal_abl" if explain_fn == "modal_abl" else "ixg"
     acc = defaultdict(list)
     modals = list(modals)
     for batch in loader:
@@ -55,19 +110,26 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
         ys = torch.as_tensor(batch["target"])
         with torch.no_grad():
             xs = tuple(downscale_inputs(xs, downscale))
-        attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
+        if explain_fn == "modal_abl":
+            attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
+        else:
+            grads = input_gradients(model, xs, ys.squeeze())
+            attrs = input_x_grad_totals(xs, grads).to("cpu")
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, tuple(x.detach() * g for x, g in zip(xs, grads)))
         acc["exam_knee_id"].extend(batch[("-", "exam_knee_id")])
         acc["target"].extend(ys.to("cpu").numpy().tolist())
         acc["modal_names"].extend([modals, ] * attrs.shape[0])
-        acc["modal_abl_attrs"].extend(attrs.numpy().tolist())
-        acc["modal_abl_percent"].extend(ablation_percent(attrs).tolist())
+        acc[f"{field}_attrs"].extend(attrs.numpy().tolist())
+        acc[f"{field}_percent"].extend(ablation_percent(attrs).tolist())
     return dict(acc)
 
 
-def ensemble_explain_foldw(raw_foldw):
+def ensemble_explain_foldw(raw_foldw, prefix="modal_abl"):
     """Inner 1:1 merge of the folds on exam_knee_id (first fold's order; target / modal_names from the first fold),
     per-fold columns modal_abl_attrs__k / modal_abl_percent__k, and modal_abl_percent = fold mean of the per-fold
-    per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64)."""
+    per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64).
+    prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad")."""
     folds = list(raw_foldw)
     if not folds:
         raise ValueError("no folds to ensemble")
@@ -86,13 +148,13 @@ def ensemble_explain_foldw(raw_foldw):
     stack = []
     for k in folds:
         rows = [pos[k][e] for e in ids]
-        ens[f"modal_abl_attrs__{k}"] = [raw_foldw[k]["modal_abl_attrs"][r] for r in rows]
-        ens[f"modal_abl_percent__{k}"] = [raw_foldw[k]["modal_abl_percent"][r] for r in rows]
+        ens[f"{prefix}_attrs__{k}"] = [raw_foldw[k][f"{prefix}_attrs"][r] for r in rows]
+        ens[f"{prefix}_percent__{k}"] = [raw_foldw[k][f"{prefix}_percent"][r] for r in rows]
         if ids:
-            stack.append(np.asarray(ens[f"modal_abl_percent__{k}"], dtype=np.float64).reshape(len(ids), -1))
+            stack.append(np.asarray(ens[f"{prefix}_percent__{k}"], dtype=np.float64).reshape(len(ids), -1))
     if not ids:
-        ens["modal_abl_percent"] = []
+        ens[f"{prefix}_percent"] = []
         return ens
     mean = np.mean(np.stack(stack, axis=1), axis=1)                  # samples x modals
-    ens["modal_abl_percent"] = (mean / np.sum(mean, axis=1, keepdims=True)).tolist()
+    ens[f"{prefix}_percent"] = (mean / np.sum(mean, axis=1, keepdims=True)).tolist()
     return ens

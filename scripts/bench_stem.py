@@ -1,4 +1,4 @@
-"""microbench: the 7x7 / stride-2 stem (forward, weight gradient) on one encoder's slices of the synthetic shape"""
+"""microbench: the 7x7 / stride-2 stem (forward, weight gradient, data gradient) on one encoder's slices of the synthetic shape"""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -44,3 +44,12 @@ print(f"BatchNorm reduction with the pool gradient gathered {t:7.3f} ms  {(2 * y
 ap = ops.bn_bwd(None, y, saved, rows, C, rows, dg, db, 2, fused=True, pool=(dyp, am, N, H1, W1), dz_out=dz)
 t = timeit(lambda: ops.stem_wgrad(ap, x, dw, N, H, W))
 print(f"stem wgrad with the apply on load {t:7.3f} ms")
+# the data gradient (input-gradient / saliency path only) next to the weight gradient it shares its operands with: 20 launches
+# back to back each, and the time of moving the bytes once (dc0 read, dx written) at the 6.3 TB/s a float4 copy reaches on this chip
+tw = timeit(lambda: ops.stem_wgrad(dy, x, dw, N, H, W), n=20)
+td = timeit(lambda: ops.stem_dgrad(dy, w1t, N, H, W), n=20)
+floor = (y.numel() + x.numel()) * 4 / 6.3e9
+print(f"stem dgrad {td:7.3f} ms  ({12.25 * 64 * 2 * x.numel() / td / 1e9:6.1f} TFLOP/s of the sum's own FMAs, {(y.numel() + x.numel()) * 4 / td / 1e9:5.2f} TB/s)  "
+      f"stem wgrad {tw:7.3f} ms  ratio {td / tw:4.2f}  floor (dc0 once + dx) {floor:6.3f} ms")
+ta = timeit(lambda: ops.stem_dgrad(ap, w1t, N, H, W), n=20)
+print(f"stem dgrad with the apply on load {ta:7.3f} ms  (reads dz and c0: floor {(2 * y.numel() + x.numel()) * 4 / 6.3e9:6.3f} ms)")
