@@ -632,6 +632,24 @@ int koaf_rmsprop_step(float* p, const float* g, float* sq, float* gavg, float* b
  * hyper[2] = {*lr, *step == 1 ? 1 : 0}. */
 int koaf_optim_hyper(int32_t* step, const float* lr, float* hyper, void* stream);
 
+/* ---- gradient accumulation over micro-batches and global-norm clipping (torch.nn.utils.clip_grad_norm_) over flat fp32
+ * ranges of the arena: 16-byte aligned, any n.  Every block owns one fixed chunk of the range and every reduction is
+ * fixed-order and two-stage (no atomics): the same bits from run to run.  Nothing reads a value back to the host.
+ * norm_kind: 0 = 2-norm (each square and the sums in fp64: |g| ~ 1e25 does not overflow), 1 = inf-norm (integer maximum over
+ * the magnitude bits: a NaN anywhere reaches the result).
+ * koaf_grad_fold  mode 0: acc = w * g;  1: acc = acc + w * g;  2: g = acc + w * g (acc unchanged).  The product is rounded to
+ *   fp32, then the sum (no fused multiply-add).  ws (nullable, mode 2 only): koaf_grad_norm_ws(n) floats, receives the block
+ *   partials of the norm of the values written to g, as koaf_grad_norm_part would give them.
+ * koaf_grad_norm_part  the block partials of g's norm -> ws (koaf_grad_norm_ws(n) floats, 8-byte aligned).
+ * koaf_grad_norm_final  ws: the partials of one or several ranges laid end to end, nws floats in all, combined in index order
+ *   -> norm[0];  coef[0] (nullable) = min(1, max_norm / (norm + 1e-6f)) in fp32 as written: a NaN norm gives NaN, +Inf gives 0.
+ * koaf_grad_scale  g *= coef[0] (a device scalar); a block leaves without touching memory when coef[0] == 1. */
+int64_t koaf_grad_norm_ws(int64_t n);
+int koaf_grad_fold(float* acc, float* g, int64_t n, float w, int32_t mode, int32_t norm_kind, float* ws, void* stream);
+int koaf_grad_norm_part(const float* g, int64_t n, int32_t norm_kind, float* ws, void* stream);
+int koaf_grad_norm_final(const float* ws, int64_t nws, int32_t norm_kind, float max_norm, float* norm, float* coef, void* stream);
+int koaf_grad_scale(float* g, int64_t n, const float* coef, void* stream);
+
 /* ---- nn.BCELoss / nn.BCEWithLogitsLoss (_losses.py:111-117, the "bce_loss" / "bce_wlogits_loss" keys) ----
  * x, target [n] (any equal shape, flattened), weight [n] (already expanded to x's shape) or NULL, pos_weight [C] or NULL (logits
  * form only; C = the last dimension, n % C == 0).  Loss and gradient in one launch:

@@ -204,9 +204,42 @@ def grad_target(p):
     return t, p.grad is not None
 
 
+def _same_flat_memory(a, b):
+    """two fp32 device tensors over one dense memory layout (contiguous, or both packed conv weights), 16-byte aligned"""
+    if not (a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float32 and a.shape == b.shape and a.stride() == b.stride()):
+        return False
+    return (a.is_contiguous() or is_packed(a)) and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0
+
+
+def _flat(t):
+    return (t.permute(0, 2, 3, 1) if t.dim() == 4 and not t.is_contiguous() else t).reshape(-1)
+
+
+def grads_by_arena(params):
+    """-> {id(arena): (arena, [parameters with a gradient])} with every `.grad` the parameter's view of arena.G (a foreign
+    gradient tensor is copied in, as the optimizers do); a parameter outside any arena raises"""
+    by_arena = {}
+    for p in params:
+        if p.grad is None:
+            continue
+        a = getattr(p, "_koaf_arena", None)
+        if a is None or not a.valid():
+            raise RuntimeError("this parameter lives outside the model's arena (run one forward of the model first)")
+        gv = p._koaf_grad
+        if p.grad.data_ptr() != gv.data_ptr():
+            gv.copy_(p.grad)
+            p.grad = gv
+        by_arena.setdefault(id(a), (a, []))[1].append(p)
+    return by_arena
+
+
 def deliver_grad(p, buf, accumulate):
     if accumulate:
-        p.grad.add_(buf)
+        if _same_flat_memory(p.grad, buf):
+            from . import ops
+            ops.grad_fold(_flat(p.grad), _flat(buf), 1.0, 1)      # p.grad += buf: the same one fp32 addition per element
+        else:
+            p.grad.add_(buf)
     else:
         p.grad = buf
     a = getattr(p, "_koaf_arena", None)

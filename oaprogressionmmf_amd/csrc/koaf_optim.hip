@@ -2,6 +2,7 @@
 // streams over the flat parameter arena, shaped like adam_kernel (koaf_elem.hip): 16-byte loads and stores, a grid-stride loop,
 // a scalar tail; every operand is read once and every updated one written once.  The options that do not change from launch to
 // launch (momentum / Nesterov / centered / ...) are template parameters, so each variant carries only its own loads and stores.
+// Below them: what sits between backward and the optimizer step -- the gradient fold of micro-batched steps and global-norm clipping.
 #include "koaf_common.h"
 
 namespace {
@@ -133,6 +134,165 @@ __global__ void __launch_bounds__(256) rmsprop_kernel(float* __restrict__ p, con
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gradient accumulation over micro-batches and global-norm clipping, on flat fp32 ranges of the arena.  Streaming kernels
+// shaped like the ones above (16-byte accesses, a scalar tail), but every block owns one FIXED chunk of GN_CHUNK elements:
+// the norm is a two-stage reduction whose partials (one per chunk, slot = chunk index) must not depend on the grid, so that
+// the bits repeat from run to run.  No atomics anywhere.
+//   fold     mode 0: acc = w * g;  1: acc = acc + w * g;  2: g = acc + w * g (the last micro-batch, written back into G, and
+//            optionally the norm partials of what it writes).  Product and sum are rounded separately (contraction off: no fused multiply-add),
+//            so that numpy restates them: np.float32(w) * g, then +.
+//   norm     2-norm: squares and sums in fp64 (the square of an fp32 value is exact there and cannot overflow);
+//            inf-norm: an integer maximum over the magnitude bits (koaf_absbits: a NaN compares above +Inf and survives).
+//   final    one block adds / maximises all partials in index order -> norm[0], coef[0] = min(1, max_norm / (norm + 1e-6f))
+//   scale    g *= coef[0] read from the device; a block whose coef is exactly 1 leaves without touching memory.
+// ------------------------------------------------------------------------------------------------
+constexpr int GN_CHUNK = 16384;         // elements per block (64 KiB per operand: 16 dwordx4 accesses per lane)
+constexpr int GN_NONE = -1, GN_L2 = 0, GN_INF = 1;
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// one norm term: KIND GN_L2 adds x^2 to sq, GN_INF raises mx to |x|'s bits
+template <int KIND>
+__device__ __forceinline__ void gn_term(float x, double& sq, unsigned& mx) {
+    if constexpr (KIND == GN_L2) sq += (double)x * (double)x;
+    if constexpr (KIND == GN_INF) { const unsigned b = koaf_absbits(x); mx = mx > b ? mx : b; }
+}
+
+// the block's partial -> its 8-byte workspace slot (an fp64 sum, or the magnitude bits widened to 64): fixed lane / wave order
+template <int KIND>
+__device__ __forceinline__ void gn_block_partial(double sq, unsigned mx, void* __restrict__ ws) {
+    if constexpr (KIND == GN_L2) {
+        __shared__ double red[4];
+        sq = wave_sum_f64(sq);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+        __syncthreads();
+        if (threadIdx.x == 0) ((double*)ws)[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+    if constexpr (KIND == GN_INF) {
+        __shared__ unsigned redu[4];
+        mx = wave_max_u(mx);
+        if ((threadIdx.x & 63) == 0) redu[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned m = redu[0];
+            for (int i = 1; i < 4; ++i) m = m > redu[i] ? m : redu[i];
+            ((unsigned long long*)ws)[blockIdx.x] = m;
+        }
+    }
+}
+
+template <int MODE>
+__device__ __forceinline__ float fold_one(float a, float g, float w) {
+#pragma clang fp contract(off)          // the product rounds first: no fma (hipcc contracts __fmul_rn + __fadd_rn like any a * b + c)
+    const float wg = w * g;
+    return MODE == 0 ? wg : a + wg;
+}
+
+template <int MODE, int KIND>
+__global__ void __launch_bounds__(256) grad_fold_kernel(float* __restrict__ acc, float* __restrict__ g, int64_t n, float w,
+                                                        void* __restrict__ ws) {
+    const int64_t e0 = (int64_t)blockIdx.x * GN_CHUNK, e1 = e0 + GN_CHUNK < n ? e0 + GN_CHUNK : n;
+    const int64_t v1 = e1 / 4;          // (e0 is a multiple of 4: only the last block has a scalar tail)
+    float* __restrict__ dst = MODE == 2 ? g : acc;
+    double sq = 0.0;
+    unsigned mx = 0u;
+#pragma unroll 4
+    for (int64_t i = e0 / 4 + threadIdx.x; i < v1; i += EB) {
+        const v4f gv = *(const v4f*)&g[i * 4];
+        v4f av = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (MODE != 0) av = *(const v4f*)&acc[i * 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            av[j] = fold_one<MODE>(av[j], gv[j], w);
+            gn_term<KIND>(av[j], sq, mx);
+        }
+        *(v4f*)&dst[i * 4] = av;
+    }
+    const int64_t i = v1 * 4 + threadIdx.x;
+    if (i < e1) {
+        const float r = fold_one<MODE>(MODE != 0 ? acc[i] : 0.f, g[i], w);
+        gn_term<KIND>(r, sq, mx);
+        dst[i] = r;
+    }
+    gn_block_partial<KIND>(sq, mx, ws);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) grad_norm_part_kernel(const float* __restrict__ g, int64_t n, void* __restrict__ ws) {
+    const int64_t e0 = (int64_t)blockIdx.x * GN_CHUNK, e1 = e0 + GN_CHUNK < n ? e0 + GN_CHUNK : n;
+    const int64_t v1 = e1 / 4;
+    double sq = 0.0;
+    unsigned mx = 0u;
+#pragma unroll 4
+    for (int64_t i = e0 / 4 + threadIdx.x; i < v1; i += EB) {
+        const v4f gv = *(const v4f*)&g[i * 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gn_term<KIND>(gv[j], sq, mx);
+    }
+    const int64_t i = v1 * 4 + threadIdx.x;
+    if (i < e1) gn_term<KIND>(g[i], sq, mx);
+    gn_block_partial<KIND>(sq, mx, ws);
+}
+
+// all partials (of every range, laid end to end) -> norm, coef.  Lane t takes slots t, t + 256, ... in rising order, then the
+// fixed wave / block order: the same bits whatever the scheduling.  c > 1 ? 1 : c keeps a NaN (fminf would drop it).
+template <int KIND>
+__global__ void __launch_bounds__(256) grad_norm_final_kernel(const void* __restrict__ ws, int64_t nparts, float max_norm,
+                                                              float* __restrict__ norm, float* __restrict__ coef) {
+    double sq = 0.0;
+    unsigned mx = 0u;
+    for (int64_t i = threadIdx.x; i < nparts; i += EB) {
+        if constexpr (KIND == GN_L2) sq += ((const double*)ws)[i];
+        if constexpr (KIND == GN_INF) { const unsigned b = (unsigned)((const unsigned long long*)ws)[i]; mx = mx > b ? mx : b; }
+    }
+    float nv;
+    if constexpr (KIND == GN_L2) {
+        __shared__ double red[4];
+        sq = wave_sum_f64(sq);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+        __syncthreads();
+        nv = (float)sqrt(((red[0] + red[1]) + red[2]) + red[3]);
+    } else {
+        __shared__ unsigned redu[4];
+        mx = wave_max_u(mx);
+        if ((threadIdx.x & 63) == 0) redu[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        unsigned m = redu[0];
+        for (int i = 1; i < 4; ++i) m = m > redu[i] ? m : redu[i];
+        nv = __uint_as_float(m);
+    }
+    if (threadIdx.x == 0) {
+        norm[0] = nv;
+        if (coef) {
+            const float c = __fdiv_rn(max_norm, __fadd_rn(nv, 1e-6f));
+            coef[0] = c > 1.f ? 1.f : c;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) grad_scale_kernel(float* __restrict__ g, int64_t n, const float* __restrict__ coef) {
+    const float c = coef[0];
+    if (c == 1.f) return;               // not clipped: one scalar read per block, no traffic
+    const int64_t e0 = (int64_t)blockIdx.x * GN_CHUNK, e1 = e0 + GN_CHUNK < n ? e0 + GN_CHUNK : n;
+    const int64_t v1 = e1 / 4;
+#pragma unroll 4
+    for (int64_t i = e0 / 4 + threadIdx.x; i < v1; i += EB) {
+        v4f gv = *(const v4f*)&g[i * 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = __fmul_rn(gv[j], c);
+        *(v4f*)&g[i * 4] = gv;
+    }
+    const int64_t i = v1 * 4 + threadIdx.x;
+    if (i < e1) g[i] = __fmul_rn(g[i], c);
+}
+
+inline int64_t gn_blocks(int64_t n) { return cdiv64(n, GN_CHUNK); }
+
 }  // namespace
 
 // ================================================================================================
@@ -183,4 +343,57 @@ extern "C" int koaf_rmsprop_step(float* p, const float* g, float* sq, float* gav
     else KOAF_RMS(false, false);
 #undef KOAF_RMS
     return koaf_check_launch("koaf_rmsprop_step");
+}
+
+extern "C" int64_t koaf_grad_norm_ws(int64_t n) { return n > 0 ? 2 * gn_blocks(n) : 0; }      // (one 8-byte partial per block)
+
+extern "C" int koaf_grad_fold(float* acc, float* g, int64_t n, float w, int32_t mode, int32_t norm_kind, float* ws, void* stream) {
+    KOAF_REQUIRE(acc && g && n > 0, "koaf_grad_fold: bad args");
+    KOAF_REQUIRE(mode >= 0 && mode <= 2, "koaf_grad_fold: mode is 0 (acc = w g), 1 (acc += w g) or 2 (g = acc + w g)");
+    KOAF_REQUIRE(!ws || (mode == 2 && (norm_kind == GN_L2 || norm_kind == GN_INF)),
+                 "koaf_grad_fold: norm partials come with mode 2 and a norm kind of 0 (2-norm) or 1 (inf-norm)");
+    KOAF_REQUIRE(aligned16(acc) && aligned16(g), "koaf_grad_fold: unaligned");
+    KOAF_REQUIRE((((uintptr_t)ws) & 7) == 0, "koaf_grad_fold: the workspace is 8-byte aligned");
+    KOAF_REQUIRE(gn_blocks(n) < (1ll << 31), "koaf_grad_fold: range too long");
+    const dim3 grid((unsigned)gn_blocks(n)), block(EB);
+#define KOAF_FOLD(MODE, KIND) hipLaunchKernelGGL((grad_fold_kernel<MODE, KIND>), grid, block, 0, STREAM, acc, g, n, w, (void*)ws)
+    if (mode == 0) KOAF_FOLD(0, GN_NONE);
+    else if (mode == 1) KOAF_FOLD(1, GN_NONE);
+    else if (!ws) KOAF_FOLD(2, GN_NONE);
+    else if (norm_kind == GN_L2) KOAF_FOLD(2, GN_L2);
+    else KOAF_FOLD(2, GN_INF);
+#undef KOAF_FOLD
+    return koaf_check_launch("koaf_grad_fold");
+}
+
+extern "C" int koaf_grad_norm_part(const float* g, int64_t n, int32_t norm_kind, float* ws, void* stream) {
+    KOAF_REQUIRE(g && ws && n > 0, "koaf_grad_norm_part: bad args");
+    KOAF_REQUIRE(norm_kind == GN_L2 || norm_kind == GN_INF, "koaf_grad_norm_part: the norm kind is 0 (2-norm) or 1 (inf-norm)");
+    KOAF_REQUIRE(aligned16(g), "koaf_grad_norm_part: unaligned");
+    KOAF_REQUIRE((((uintptr_t)ws) & 7) == 0, "koaf_grad_norm_part: the workspace is 8-byte aligned");
+    KOAF_REQUIRE(gn_blocks(n) < (1ll << 31), "koaf_grad_norm_part: range too long");
+    const dim3 grid((unsigned)gn_blocks(n)), block(EB);
+    if (norm_kind == GN_L2) hipLaunchKernelGGL(grad_norm_part_kernel<GN_L2>, grid, block, 0, STREAM, g, n, (void*)ws);
+    else hipLaunchKernelGGL(grad_norm_part_kernel<GN_INF>, grid, block, 0, STREAM, g, n, (void*)ws);
+    return koaf_check_launch("koaf_grad_norm_part");
+}
+
+extern "C" int koaf_grad_norm_final(const float* ws, int64_t nws, int32_t norm_kind, float max_norm, float* norm, float* coef,
+                                    void* stream) {
+    KOAF_REQUIRE(ws && norm && nws > 0 && (nws & 1) == 0, "koaf_grad_norm_final: bad args");
+    KOAF_REQUIRE(norm_kind == GN_L2 || norm_kind == GN_INF, "koaf_grad_norm_final: the norm kind is 0 (2-norm) or 1 (inf-norm)");
+    KOAF_REQUIRE((((uintptr_t)ws) & 7) == 0, "koaf_grad_norm_final: the workspace is 8-byte aligned");
+    if (norm_kind == GN_L2)
+        hipLaunchKernelGGL(grad_norm_final_kernel<GN_L2>, dim3(1), dim3(EB), 0, STREAM, (const void*)ws, nws / 2, max_norm, norm, coef);
+    else
+        hipLaunchKernelGGL(grad_norm_final_kernel<GN_INF>, dim3(1), dim3(EB), 0, STREAM, (const void*)ws, nws / 2, max_norm, norm, coef);
+    return koaf_check_launch("koaf_grad_norm_final");
+}
+
+extern "C" int koaf_grad_scale(float* g, int64_t n, const float* coef, void* stream) {
+    KOAF_REQUIRE(g && coef && n > 0, "koaf_grad_scale: bad args");
+    KOAF_REQUIRE(aligned16(g), "koaf_grad_scale: unaligned");
+    KOAF_REQUIRE(gn_blocks(n) < (1ll << 31), "koaf_grad_scale: range too long");
+    hipLaunchKernelGGL(grad_scale_kernel, dim3((unsigned)gn_blocks(n)), dim3(EB), 0, STREAM, g, n, coef);
+    return koaf_check_launch("koaf_grad_scale");
 }

@@ -898,6 +898,66 @@ def optim_hyper(step, lr, hyper):
     check(lib().koaf_optim_hyper(step.data_ptr(), _ptr(lr), _ptr(hyper), _stream()), "optim_hyper")
 
 
+def norm_kind(norm_type):
+    """torch's norm_type -> the library's norm kind: 0 for the 2-norm, 1 for the inf-norm; anything else is a ValueError"""
+    nt = float(norm_type)
+    if nt == 2.0:
+        return 0
+    if nt == float("inf"):
+        return 1
+    raise ValueError(f"norm_type {norm_type!r}: the gradient norm kernels know 2 and inf")
+
+
+def _flat32(name, *ts):
+    for t in ts:
+        _ptr(t)                                  # (CPU tensors stop here)
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous()):
+            raise KoafError(f"{name}: flat contiguous fp32 tensors only")
+
+
+def grad_norm_ws(sizes, device):
+    """-> (ws, [one slice of it per range]): the float64 workspace of the norm partials of ranges of `sizes` elements, laid end
+    to end for one grad_norm_final (one 8-byte slot per block: koaf_grad_norm_ws)"""
+    L = lib()
+    slots = [L.koaf_grad_norm_ws(int(n)) // 2 for n in sizes]
+    ws = torch.empty(sum(slots), device=device, dtype=torch.float64)
+    cuts, o = [], 0
+    for s in slots:
+        cuts.append(ws[o:o + s])
+        o += s
+    return ws, cuts
+
+
+def grad_fold(acc, g, w, mode, ws=None, norm_type=2.0):
+    """mode 0: acc = w * g;  1: acc += w * g;  2: g = acc + w * g, and with `ws` (its slice from grad_norm_ws) the norm partials of the new g.
+    Flat fp32 device tensors of one length; product and sum are rounded separately."""
+    _flat32("grad_fold", acc, g)
+    if acc.numel() != g.numel():
+        raise KoafError(f"grad_fold: {acc.numel()} and {g.numel()} elements")
+    check(lib().koaf_grad_fold(_ptr(acc), _ptr(g), g.numel(), w, mode, norm_kind(norm_type) if ws is not None else 0, _ptr(ws),
+                               _stream()), "grad_fold")
+
+
+def grad_norm_part(g, ws, norm_type=2.0):
+    """block partials of the norm of the flat fp32 device tensor g -> ws (its slice from grad_norm_ws)"""
+    _flat32("grad_norm_part", g)
+    check(lib().koaf_grad_norm_part(_ptr(g), g.numel(), norm_kind(norm_type), _ptr(ws), _stream()), "grad_norm_part")
+
+
+def grad_norm_final(ws, max_norm, norm_type=2.0):
+    """every partial of ws (one or several ranges, end to end) -> (norm, coef) device scalars, coef = min(1, max_norm / (norm + 1e-6))"""
+    out = torch.empty(2, device=ws.device, dtype=torch.float32)
+    check(lib().koaf_grad_norm_final(_ptr(ws), 2 * ws.numel(), norm_kind(norm_type), max_norm, _ptr(out[0:1]), _ptr(out[1:2]),
+                                     _stream()), "grad_norm_final")
+    return out[0], out[1]
+
+
+def grad_scale(g, coef):
+    """g *= coef (a device scalar) in place; no memory traffic when coef is exactly 1"""
+    _flat32("grad_scale", g)
+    check(lib().koaf_grad_scale(_ptr(g), g.numel(), _ptr(coef), _stream()), "grad_scale")
+
+
 _BCE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 
 

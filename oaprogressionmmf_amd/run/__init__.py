@@ -3,9 +3,10 @@ path.  The drivers themselves (hydra, data loaders, tensorboard, metrics) stay t
 from ._steps import downscale_inputs, train_epoch, train_step, predict_batch
 from ._eval import eval_epoch, ensemble_eval_foldw, InferenceTimer
 from ._graph import GraphedPredictor, GraphedTrainStep
+from ._accum import GradientFold, micro_batch_weights, train_step_accum
 from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ablation_percent, input_gradients,
                        saliency_maps)
 
 __all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
-           "ablation_percent", "input_gradients", "saliency_maps"]
+           "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum"]

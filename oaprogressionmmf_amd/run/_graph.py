@@ -60,15 +60,19 @@ class GraphedTrainStep(object):
     buffers and replay.  Eager and replayed steps are the same kernels on the same device-resident step state, so a run
     is bit-identical whether or not (and when) it switches to replay.  `optimizer` must be a registry optimizer (Adam / AdamW / SGD / RMSprop) with capturable=True;
     `model` a registry model on one GPU (the RCCL exchange of DataParallelRCCL is not captured).  The returned tensors are
-    owned by the graph and overwritten by the next call.  Learning-rate changes (schedulers) are picked up at every call."""
+    owned by the graph and overwritten by the next call.  Learning-rate changes (schedulers) are picked up at every call.
+    max_grad_norm: as train_step's -- the clip (norm, coefficient and scale all on the device) is captured with the step, and
+    the norm comes back as a third value."""
 
-    def __init__(self, model, loss_fn, optimizer, example_xs, example_ys, downscale=None, warmup=2, seed=None):
+    def __init__(self, model, loss_fn, optimizer, example_xs, example_ys, downscale=None, warmup=2, seed=None, *,
+                 max_grad_norm=None):
         if not getattr(optimizer, "capturable", False):
             raise RuntimeError("GraphedTrainStep needs a registry optimizer with capturable=True (Adam / AdamW / SGD / RMSprop): step count "
                                "and learning rate on the device")
         if hasattr(model, "reduce_gradients"):
             raise RuntimeError("GraphedTrainStep captures single-GPU steps (the RCCL gradient exchange is not captured)")
         self.model, self.loss_fn, self.opt, self.downscale = model, loss_fn, optimizer, downscale
+        self.max_grad_norm = max_grad_norm
         self.xs = [x.detach().clone().contiguous() for x in example_xs]
         self.ys = example_ys.detach().clone().contiguous()
         if not all(x.is_cuda for x in self.xs):
@@ -87,7 +91,8 @@ class GraphedTrainStep(object):
         side, _encoder.USE_SIDE_STREAM = _encoder.USE_SIDE_STREAM, False
         try:
             self.state.begin_step()
-            return train_step(self.model, self.loss_fn, self.opt, self.xs, self.ys, self.downscale)
+            return train_step(self.model, self.loss_fn, self.opt, self.xs, self.ys, self.downscale,
+                              max_grad_norm=self.max_grad_norm)
         finally:
             KF.STEP_STATE = prev
             _encoder.USE_SIDE_STREAM = side

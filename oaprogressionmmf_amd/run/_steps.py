@@ -4,6 +4,7 @@ import torch
 
 from .. import ops, preproc
 from .._lib import KoafError
+from ..various._clip import clip_grad_norm_
 
 
 def downscale_inputs(xs, factors):
@@ -19,10 +20,13 @@ def downscale_inputs(xs, factors):
     return tuple(out)
 
 
-def train_step(model, loss_fn, optimizer, xs, ys, downscale=None):
+def train_step(model, loss_fn, optimizer, xs, ys, downscale=None, *, max_grad_norm=None):
     """zero_grad -> forward -> loss -> backward -> (all-reduce) -> Adam, the optimize branch of
     train_prog_fus.py:132-168.  `model` may be a registry model or a DataParallelRCCL wrapper.
-    Returns (logits, loss), both on the device; nothing here synchronises the host."""
+    Returns (logits, loss), both on the device; nothing here synchronises the host.
+    max_grad_norm (an extension, the reference has no key for it): clip the optimizer's gradients to this total 2-norm between
+    the exchange and the update (various.clip_grad_norm_: every rank clips by the same coefficient); the norm, a device
+    scalar, is then returned as a third value.  None: not one launch more than without the argument."""
     xs = downscale_inputs(xs, downscale)
     optimizer.zero_grad()
     logits = model(*xs)["main"]
@@ -32,6 +36,10 @@ def train_step(model, loss_fn, optimizer, xs, ys, downscale=None):
     reduce = getattr(model, "reduce_gradients", None)
     if reduce is not None:
         reduce()
+    if max_grad_norm is not None:
+        norm = clip_grad_norm_([p for group in optimizer.param_groups for p in group["params"]], max_grad_norm)
+        optimizer.step()
+        return logits.detach(), loss.detach(), norm
     optimizer.step()
     return logits.detach(), loss.detach()
 
