@@ -585,6 +585,8 @@ int koaf_dropout2d(const float* x, float* y, int32_t N, int32_t HW, int32_t C, f
                    const int64_t* epoch, void* stream);
 /* out = a + b */
 int koaf_add(const float* a, const float* b, float* out, int64_t n, void* stream);
+/* p[0..n) = value */
+int koaf_fill(float* p, float value, int64_t n, void* stream);
 /* column sums of x [rows][C] -> out [C] (bias gradients); part: koaf_colsum_ws floats or NULL */
 int64_t koaf_colsum_ws(int32_t rows, int32_t C);
 int koaf_colsum(const float* x, float* out, int32_t rows, int32_t C, float* part, void* stream);
@@ -611,7 +613,6 @@ int koaf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
 /* Device-resident optimizer step state for captured (HIP-graph) train steps: ++*step; hyper[3] = {lr, lr / (1 - beta1^step),
  * sqrt(1 - beta2^step)} from the device scalars; hand `hyper` to koaf_adam_step (its host lr / step are then ignored). */
 int koaf_adam_hyper(int32_t* step, const float* lr, double beta1, double beta2, float* hyper, void* stream);
-int koaf_fill(float* p, float value, int64_t n, void* stream);
 
 /* ---- torch.optim.SGD over a flat arena (_optimizers.py:47-52, the "SGD" key) -------------------
  * g' = (maximize ? -g : g) + weight_decay * p;  with a momentum: buf = first ? g' : momentum * buf + (1 - dampening) * g' and

@@ -1,5 +1,5 @@
 // koaf_elem.hip -- HBM-bound kernels of the koafusion train step: BatchNorm statistics / backward,
-// bottleneck tail, max-pool, GAP, LayerNorm, softmax, GELU, dropout, focal loss, Adam, layout moves.
+// bottleneck tail, max-pool, GAP, LayerNorm, softmax, GELU, dropout, focal loss, layout moves.
 // All are float4-vectorised along the channel (fastest) axis and sized for >= 8 blocks per CU.
 #include <stdarg.h>
 #include "koaf_common.h"
@@ -1129,70 +1129,6 @@ __global__ void __launch_bounds__(256) loss_grid_sum_kernel(const float* __restr
     if (threadIdx.x == 0) *out = red[0] * (wden ? 1.f / *wden : (nden > 0.f ? 1.f / nden : 1.f));
 }
 
-// ------------------------------------------------------------------------------------------------
-// Adam (torch.optim.Adam single-tensor update rule, coupled L2; adamw: decoupled)
-// ------------------------------------------------------------------------------------------------
-// ++step; hyper = {lr, lr / (1 - b1^step), sqrt(1 - b2^step)}: what koaf_adam_step derives on the host from (lr, step), derived
-// on the device so that a captured (HIP-graph) optimizer step advances from replay to replay
-__global__ void adam_hyper_kernel(int32_t* step, const float* lr, double b1, double b2, float* hyper) {
-    const int st = *step + 1;
-    *step = st;
-    const double bc1 = 1.0 - pow(b1, (double)st), bc2 = 1.0 - pow(b2, (double)st);
-    hyper[0] = *lr;
-    hyper[1] = (float)((double)*lr / bc1);
-    hyper[2] = (float)sqrt(bc2);
-}
-
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                   float omb1, float b2, float omb2, float eps, float wd, float step_size,
-                                                   float bc2_sqrt, int adamw, const float* __restrict__ hyper,
-                                                   float* __restrict__ vmax) {
-    // (omb1 = 1 - beta1 and omb2 = 1 - beta2 arrive rounded from the DOUBLE differences, as torch forms them: 1.f - 0.999f is
-    // 1.3e-5 away from float(1 - 0.999), which showed in the second moments)
-    if (hyper) { lr = hyper[0]; step_size = hyper[1]; bc2_sqrt = hyper[2]; }   // device-resident step state (koaf_adam_hyper)
-    const int64_t nvec = n / 4;
-    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * EB) {
-        v4f pv = *(const v4f*)&p[i * 4], gv = *(const v4f*)&g[i * 4];
-        v4f mv = *(const v4f*)&m[i * 4], vv = *(const v4f*)&v[i * 4];
-        v4f xv = {0.f, 0.f, 0.f, 0.f};
-        if (vmax) xv = *(const v4f*)&vmax[i * 4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gj = gv[j], pj = pv[j];
-            if (adamw) pj *= (1.f - lr * wd);
-            else gj += wd * pj;
-            const float mj = mv[j] + (gj - mv[j]) * omb1;
-            const float vj = vv[j] * b2 + omb2 * gj * gj;
-            float vd = vj;
-            if (vmax) { vd = fmaxf(xv[j], vj); xv[j] = vd; }     // amsgrad: the running maximum of the second moment
-            const float denom = sqrtf(vd) / bc2_sqrt + eps;
-            pv[j] = pj - step_size * (mj / denom);
-            mv[j] = mj;
-            vv[j] = vj;
-        }
-        *(v4f*)&p[i * 4] = pv;
-        *(v4f*)&m[i * 4] = mv;
-        *(v4f*)&v[i * 4] = vv;
-        if (vmax) *(v4f*)&vmax[i * 4] = xv;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-        const int64_t i = nvec * 4 + threadIdx.x;
-        float gj = g[i], pj = p[i];
-        if (adamw) pj *= (1.f - lr * wd);
-        else gj += wd * pj;
-        const float mj = m[i] + (gj - m[i]) * omb1;
-        const float vj = v[i] * b2 + omb2 * gj * gj;
-        float vd = vj;
-        if (vmax) { vd = fmaxf(vmax[i], vj); vmax[i] = vd; }
-        p[i] = pj - step_size * (mj / (sqrtf(vd) / bc2_sqrt + eps));
-        m[i] = mj;
-        v[i] = vj;
-    }
-}
-
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 // ================================================================================================
@@ -1244,7 +1180,7 @@ extern "C" int koaf_bn_finalize(const float* stats, int32_t rows, int32_t C, int
 extern "C" int koaf_bn_add_relu(const float* c, const float* sc, const float* sh, const float* idt, const float* idsc,
                                 const float* idsh, float* y, int64_t rows, int32_t C, int32_t act16, void* stream) {
     KOAF_REQUIRE(c && sc && sh && y && rows > 0 && C > 0 && C % 4 == 0, "koaf_bn_add_relu: bad args");
-    KOAF_REQUIRE(al16(c) && al16(y) && al16(sc) && al16(sh) && (!idt || al16(idt)), "koaf_bn_add_relu: unaligned");
+    KOAF_REQUIRE(aligned16(c) && aligned16(y) && aligned16(sc) && aligned16(sh) && (!idt || aligned16(idt)), "koaf_bn_add_relu: unaligned");
     KOAF_REQUIRE((idsc == nullptr) == (idsh == nullptr), "koaf_bn_add_relu: idsc/idsh come together");
     const int64_t nvec = rows * (C / 4);
     if (act16) hipLaunchKernelGGL(bn_add_relu_kernel<true>, dim3(ew_grid(nvec)), dim3(EB), 0, STREAM, c, sc, sh, idt, idsc, idsh, y,
@@ -1465,7 +1401,7 @@ extern "C" int koaf_augment(const float* x, float* y, const float* mm, const flo
                             int32_t C, int32_t S, float mean, float stdv, void* stream) {
     KOAF_REQUIRE(x && y && mm && params && B > 0 && R > 0 && C > 0 && S > 0, "koaf_augment: bad args");
     KOAF_REQUIRE((int64_t)R * C * S < (1ll << 31), "koaf_augment: sample too large");
-    const bool v4 = (S % 4 == 0) && al16(x) && al16(y);
+    const bool v4 = (S % 4 == 0) && aligned16(x) && aligned16(y);
     const int64_t total = (int64_t)B * R * C * (v4 ? S / 4 : S);
     if (v4)
         hipLaunchKernelGGL(augment_kernel<4>, dim3(ew_grid(total)), dim3(EB), 0, STREAM, x, y, mm, params, B, R, C, S, mean, stdv);
@@ -1515,7 +1451,7 @@ extern "C" int koaf_softmax_bwd_rows(float* dp, const float* p, int64_t rows, in
 
 #define PW_LAUNCH(OP, a, b, out, n, name)                                                                      \
     KOAF_REQUIRE((a) && (out) && (n) > 0, name ": bad args");                                                  \
-    KOAF_REQUIRE(al16(a) && al16(out) && (!(b) || al16(b)), name ": unaligned");                               \
+    KOAF_REQUIRE(aligned16(a) && aligned16(out) && (!(b) || aligned16(b)), name ": unaligned");                \
     hipLaunchKernelGGL(pointwise_kernel<OP>, dim3(ew_grid(((n) + 3) / 4)), dim3(EB), 0, STREAM, a, b, out, n); \
     return koaf_check_launch(name)
 
@@ -1539,7 +1475,7 @@ extern "C" int koaf_add(const float* a, const float* b, float* out, int64_t n, v
 }
 extern "C" int koaf_widen(const void* x, int32_t dtype, float* y, int64_t n, void* stream) {
     KOAF_REQUIRE(x && y && n > 0 && dtype >= 1 && dtype <= 3, "koaf_widen: bad args (dtype 1 = uint8, 2 = uint16, 3 = int16)");
-    KOAF_REQUIRE(al16(y) && (((uintptr_t)x) & 7) == 0, "koaf_widen: unaligned");
+    KOAF_REQUIRE(aligned16(y) && (((uintptr_t)x) & 7) == 0, "koaf_widen: unaligned");
     const unsigned grid = ew_grid(n / 4 + 1);
     if (dtype == 1) hipLaunchKernelGGL(widen_kernel<uint8_t>, dim3(grid), dim3(EB), 0, STREAM, (const uint8_t*)x, y, n);
     else if (dtype == 2) hipLaunchKernelGGL(widen_kernel<uint16_t>, dim3(grid), dim3(EB), 0, STREAM, (const uint16_t*)x, y, n);
@@ -1573,7 +1509,7 @@ extern "C" int koaf_fill(float* p, float value, int64_t n, void* stream) {
 extern "C" int koaf_colsum(const float* x, float* out, int32_t rows, int32_t C, float* part, void* stream) {
     KOAF_REQUIRE(x && out && rows > 0 && C > 0, "koaf_colsum: bad args");
     ColGeom g;
-    if (part && al16(x) && col_geom(rows, C, 256, &g)) {
+    if (part && aligned16(x) && col_geom(rows, C, 256, &g)) {
         hipLaunchKernelGGL(colstats_kernel<false>, dim3(g.nblk, g.nchunk), dim3(256), 0, STREAM, x, (int64_t)rows, C, g, part,
                            0, (const float*)nullptr);
         hipLaunchKernelGGL(colfinal_kernel<1>, dim3((C + 63) / 64), dim3(1024), 0, STREAM, part, g.nblk, C, out,
@@ -1632,24 +1568,4 @@ extern "C" int koaf_ce_loss(const float* logits, const int64_t* target, const fl
     hipLaunchKernelGGL(focal_loss_kernel, dim3(1), dim3(256), 0, STREAM, logits, target, class_weight, loss, dlogits, B, C, S,
                        0.f, 1, 0, koaf_status_ptr());
     return koaf_check_launch("koaf_ce_loss");
-}
-
-extern "C" int koaf_adam_hyper(int32_t* step, const float* lr, double beta1, double beta2, float* hyper, void* stream) {
-    KOAF_REQUIRE(step && lr && hyper, "koaf_adam_hyper: bad args");
-    hipLaunchKernelGGL(adam_hyper_kernel, dim3(1), dim3(1), 0, STREAM, step, lr, beta1, beta2, hyper);
-    return koaf_check_launch("koaf_adam_hyper");
-}
-extern "C" int koaf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1,
-                              double beta2, float eps, float weight_decay, int32_t step, int32_t adamw,
-                              const float* hyper, float* vmax, void* stream) {
-    if (hyper) step = 1;      // (lr / step come from the device; the host values are ignored)
-    KOAF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "koaf_adam_step: bad args");
-    KOAF_REQUIRE(al16(p) && al16(g) && al16(m) && al16(v) && (!vmax || al16(vmax)), "koaf_adam_step: unaligned");
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
-    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4 + 1)), dim3(EB), 0, STREAM, p, g, m, v, n, lr, (float)(1.0 - beta1),
-                       (float)beta2, (float)(1.0 - beta2), eps, weight_decay, step_size, bc2_sqrt, adamw, hyper, vmax);
-    return koaf_check_launch("koaf_adam_step");
 }

@@ -1,7 +1,8 @@
-// koaf_optim.hip -- the registry's other two optimizers (koafusion/various/_optimizers.py:47-52: "SGD", "RMSprop") as one-pass
-// streams over the flat parameter arena, shaped like adam_kernel (koaf_elem.hip): 16-byte loads and stores, a grid-stride loop,
-// a scalar tail; every operand is read once and every updated one written once.  The options that do not change from launch to
-// launch (momentum / Nesterov / centered / ...) are template parameters, so each variant carries only its own loads and stores.
+// koaf_optim.hip -- the registry's optimizers (koafusion/various/_optimizers.py:47-52: "SGD", "RMSprop", "Adam" / "AdamW") as
+// one-pass streams over the flat parameter arena: 16-byte loads and stores, a grid-stride loop, a scalar tail; every operand is
+// read once and every updated one written once.  SGD's and RMSprop's options that do not change from launch to launch (momentum /
+// Nesterov / centered / ...) are template parameters, so each variant carries only its own loads and stores; Adam's two (adamw,
+// amsgrad) are run-time arguments of its one kernel.
 // Below them: what sits between backward and the optimizer step -- the gradient fold of micro-batched steps and global-norm clipping.
 #include "koaf_common.h"
 
@@ -131,6 +132,68 @@ __global__ void __launch_bounds__(256) rmsprop_kernel(float* __restrict__ p, con
         sq[i] = sj;
         if constexpr (CEN) gavg[i] = aj;
         if constexpr (MOM) buf[i] = bj;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adam (torch.optim.Adam single-tensor update rule, coupled L2; adamw: decoupled)
+// ------------------------------------------------------------------------------------------------
+// ++step; hyper = {lr, lr / (1 - b1^step), sqrt(1 - b2^step)}: what koaf_adam_step derives on the host from (lr, step), derived
+// on the device so that a captured (HIP-graph) optimizer step advances from replay to replay
+__global__ void adam_hyper_kernel(int32_t* step, const float* lr, double b1, double b2, float* hyper) {
+    const int st = *step + 1;
+    *step = st;
+    const double bc1 = 1.0 - pow(b1, (double)st), bc2 = 1.0 - pow(b2, (double)st);
+    hyper[0] = *lr;
+    hyper[1] = (float)((double)*lr / bc1);
+    hyper[2] = (float)sqrt(bc2);
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                                   float omb1, float b2, float omb2, float eps, float wd, float step_size,
+                                                   float bc2_sqrt, int adamw, const float* __restrict__ hyper,
+                                                   float* __restrict__ vmax) {
+    // (omb1 = 1 - beta1 and omb2 = 1 - beta2 arrive rounded from the DOUBLE differences, as torch forms them: 1.f - 0.999f is
+    // 1.3e-5 away from float(1 - 0.999), which showed in the second moments)
+    if (hyper) { lr = hyper[0]; step_size = hyper[1]; bc2_sqrt = hyper[2]; }   // device-resident step state (koaf_adam_hyper)
+    const int64_t nvec = n / 4;
+    for (int64_t i = (int64_t)blockIdx.x * EB + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * EB) {
+        v4f pv = *(const v4f*)&p[i * 4], gv = *(const v4f*)&g[i * 4];
+        v4f mv = *(const v4f*)&m[i * 4], vv = *(const v4f*)&v[i * 4];
+        v4f xv = {0.f, 0.f, 0.f, 0.f};
+        if (vmax) xv = *(const v4f*)&vmax[i * 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float gj = gv[j], pj = pv[j];
+            if (adamw) pj *= (1.f - lr * wd);
+            else gj += wd * pj;
+            const float mj = mv[j] + (gj - mv[j]) * omb1;
+            const float vj = vv[j] * b2 + omb2 * gj * gj;
+            float vd = vj;
+            if (vmax) { vd = fmaxf(xv[j], vj); xv[j] = vd; }     // amsgrad: the running maximum of the second moment
+            const float denom = sqrtf(vd) / bc2_sqrt + eps;
+            pv[j] = pj - step_size * (mj / denom);
+            mv[j] = mj;
+            vv[j] = vj;
+        }
+        *(v4f*)&p[i * 4] = pv;
+        *(v4f*)&m[i * 4] = mv;
+        *(v4f*)&v[i * 4] = vv;
+        if (vmax) *(v4f*)&vmax[i * 4] = xv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t i = nvec * 4 + threadIdx.x;
+        float gj = g[i], pj = p[i];
+        if (adamw) pj *= (1.f - lr * wd);
+        else gj += wd * pj;
+        const float mj = m[i] + (gj - m[i]) * omb1;
+        const float vj = v[i] * b2 + omb2 * gj * gj;
+        float vd = vj;
+        if (vmax) { vd = fmaxf(vmax[i], vj); vmax[i] = vd; }
+        p[i] = pj - step_size * (mj / (sqrtf(vd) / bc2_sqrt + eps));
+        m[i] = mj;
+        v[i] = vj;
     }
 }
 
@@ -343,6 +406,27 @@ extern "C" int koaf_rmsprop_step(float* p, const float* g, float* sq, float* gav
     else KOAF_RMS(false, false);
 #undef KOAF_RMS
     return koaf_check_launch("koaf_rmsprop_step");
+}
+
+extern "C" int koaf_adam_hyper(int32_t* step, const float* lr, double beta1, double beta2, float* hyper, void* stream) {
+    KOAF_REQUIRE(step && lr && hyper, "koaf_adam_hyper: bad args");
+    hipLaunchKernelGGL(adam_hyper_kernel, dim3(1), dim3(1), 0, STREAM, step, lr, beta1, beta2, hyper);
+    return koaf_check_launch("koaf_adam_hyper");
+}
+extern "C" int koaf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1,
+                              double beta2, float eps, float weight_decay, int32_t step, int32_t adamw,
+                              const float* hyper, float* vmax, void* stream) {
+    if (hyper) step = 1;      // (lr / step come from the device; the host values are ignored)
+    KOAF_REQUIRE(p && g && m && v && n > 0 && step >= 1, "koaf_adam_step: bad args");
+    KOAF_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && (!vmax || aligned16(vmax)),
+                 "koaf_adam_step: unaligned");
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    const float step_size = (float)((double)lr / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    hipLaunchKernelGGL(adam_kernel, dim3(ew_grid(n / 4 + 1)), dim3(EB), 0, STREAM, p, g, m, v, n, lr, (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), eps, weight_decay, step_size, bc2_sqrt, adamw, hyper, vmax);
+    return koaf_check_launch("koaf_adam_step");
 }
 
 extern "C" int64_t koaf_grad_norm_ws(int64_t n) { return n > 0 ? 2 * gn_blocks(n) : 0; }      // (one 8-byte partial per block)

@@ -1,25 +1,51 @@
 """Optimizer / scheduler registries (reference: koafusion/various/_optimizers.py:4-67).
 
-`Adam` / `AdamW` are fused: one HIP launch per contiguous run of the flat parameter arena (for the
-reference models: one or two launches for all 389 M elements) instead of torch's per-tensor loops.  The
-update rule is torch.optim.Adam's (coupled L2 weight decay, bias-corrected).  Parameters whose `.grad` is
-None are skipped exactly like torch does (12 tensors of the cls-less aggregators never train).
-`SGD` / `RMSprop` (the registry's other two keys) run the same way on koaf_sgd_step / koaf_rmsprop_step, with torch's
-constructor signatures, update rules and state_dict layouts.  What the four share is `_ArenaOptimizer`.
+The registry's four optimizers (`SGD`, `Adam`, `AdamW`, `RMSprop`) are fused: one HIP launch per contiguous run of the flat
+parameter arena (for the reference models: one or two launches for all 389 M elements) instead of torch's per-tensor loops, on
+koaf_sgd_step / koaf_adam_step / koaf_rmsprop_step, with torch's constructor signatures, update rules (Adam: coupled L2 weight
+decay, bias-corrected) and state_dict layouts.  Parameters whose `.grad` is None are skipped exactly like torch does (SURVEY Q4:
+12 tensors of the cls-less aggregators never train).  What the four share is `_ArenaOptimizer`.
 """
 import torch
 from torch import optim
 
 from .. import ops
-from ..arena import _round_up
 
 
 class _ArenaOptimizer(optim.Optimizer):
     """What the fused optimizers share: the parameters that hold a gradient grouped by arena (foreign gradient tensors brought
-    into the arena's gradient view), the device-resident step count / learning rate of captured steps, per-parameter update
-    counts, and zero_grad's arena bookkeeping.  No CPU fallback: a CPU parameter raises."""
+    into the arena's gradient view), state buffers the size of the arena, named with torch's state_dict keys, one launch per
+    contiguous run of parameters with a gradient, loose parameters, the device-resident step count / learning rate of captured
+    steps, per-parameter update counts, torch's checkpoint layout and zero_grad's arena bookkeeping.  A subclass names the
+    buffers a group uses (`_state_names`) and launches its kernel (`_launch`); where its update depends on the parameter's
+    update count it says on what part of it (`_run_key`).  No CPU fallback: a CPU parameter raises."""
     _NAME = "optimizer"
-    _NHYPER = 3          # floats the step kernel reads from the device in a captured step (koaf_adam_hyper / koaf_optim_hyper)
+    _NHYPER = 2          # floats the step kernel reads from the device in a captured step (koaf_optim_hyper: {lr, first})
+    _HAS_STEP = False    # torch's per-parameter state carries a `step` entry
+
+    def _init_flat(self, capturable, differentiable=False):
+        if differentiable:
+            raise ValueError(f"koaf {self._NAME}: differentiable=True is not supported (the update runs in a HIP kernel outside autograd)")
+        self.capturable = bool(capturable)
+        self._dev = {}       # capturable: (id(arena), id(group)) -> device step count / lr / hyper (see _dev_state)
+        self._flat = {}      # id(arena) -> {state name: flat buffer like arena.P}
+        self._loose = {}     # id(param) -> {state name: flat buffer} for parameters outside any arena
+        self._steps = {}     # id(param) -> number of updates it has received (torch keeps `step` per parameter)
+        self._pending = {}   # id(param) -> {state name: tensor} loaded before the parameter moved into its arena
+
+    def _state_names(self, group):
+        raise NotImplementedError
+
+    def _run_key(self, n):
+        """what a launch depends on of its parameters' update count n: parameters with equal keys share launches"""
+        return False
+
+    def _hyper(self, group, d):
+        """captured steps: advance the device step count, derive what the step kernel reads from it"""
+        ops.optim_hyper(d["step"], d["lr"], d["hyper"])
+
+    def _launch(self, group, p, g, st, n, key, hyper):
+        raise NotImplementedError
 
     def _gather(self, group, loose):
         """-> {id(arena): (arena, [parameters of `group` with a gradient])}; parameters outside any arena go to loose(p)"""
@@ -79,217 +105,6 @@ class _ArenaOptimizer(optim.Optimizer):
                 if a is not None:
                     a.grad_dirty = False
 
-
-class Adam(_ArenaOptimizer):
-    _NAME = "Adam"
-    _ADAMW = False
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, capturable=False):
-        """capturable (as in torch.optim.Adam): learning rate and step count live in device memory (koaf_adam_hyper), so that
-        step() can be captured into a HIP graph and still advance on every replay (run.GraphedTrainStep); arena parameters
-        only, one shared update count (every trained parameter receives a gradient every step)."""
-        if lr < 0 or eps < 0 or weight_decay < 0:
-            raise ValueError("invalid Adam hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad)))
-        self.capturable = bool(capturable)
-        self._dev = {}       # capturable: (id(arena), group index) -> dict(step int32[1], lr float[1], hyper float[3], lr_host)
-        self._flat = {}      # id(arena) -> dict(m, v) flat moment buffers
-        self._loose = {}     # id(param) -> dict(m, v) for parameters outside any arena
-        self._steps = {}     # id(param) -> number of updates it has received (torch keeps `step` per parameter)
-        self._pending = {}   # id(param) -> (exp_avg, exp_avg_sq) loaded before the parameter moved into its arena
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if self._pending:
-            self._place_pending()            # (placement is final here: the forward that produced the gradients ran)
-        for group in self.param_groups:
-            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-            by_arena = self._gather(group, lambda p: self._step_loose(p, lr, b1, b2, eps, wd, ams=bool(group.get("amsgrad"))))
-            for a, plist in by_arena.values():
-                stt = self._arena_state(a)
-                if self.capturable:
-                    self._step_capturable(a, plist, stt, group, lr, b1, b2, eps, wd)
-                    continue
-                # the bias correction depends on the parameter's own update count: one fused launch per contiguous run
-                # of parameters with the same count (for the reference models: every trained parameter, one count)
-                by_step = {}
-                for p in plist:
-                    n = self._steps.get(id(p), 0) + 1
-                    self._steps[id(p)] = n
-                    by_step.setdefault(n, []).append(p)
-                vmax = self._vmax(stt, a.P) if group.get("amsgrad") else None
-                for n, ps in by_step.items():
-                    for lo, hi in a.active_ranges(ps):
-                        ops.adam_step(a.P[lo:hi], a.G[lo:hi], stt["m"][lo:hi], stt["v"][lo:hi], hi - lo, lr, b1, b2,
-                                      eps, wd, n, self._ADAMW, vmax=vmax[lo:hi] if vmax is not None else None)
-                a.epoch += 1             # the weights changed under the arena's plane images (arena.ensure_planes)
-        return loss
-
-    def _step_capturable(self, a, plist, stt, group, lr, b1, b2, eps, wd):
-        d = self._dev_state(a, group)
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_hyper()
-        d["params"].update(id(p) for p in plist)
-        ops.adam_hyper(d["step"], d["lr"], b1, b2, d["hyper"])
-        vmax = self._vmax(stt, a.P) if group.get("amsgrad") else None
-        for lo, hi in a.active_ranges(plist):
-            ops.adam_step(a.P[lo:hi], a.G[lo:hi], stt["m"][lo:hi], stt["v"][lo:hi], hi - lo, lr, b1, b2, eps, wd, 1,
-                          self._ADAMW, hyper=d["hyper"], vmax=vmax[lo:hi] if vmax is not None else None)
-        a.epoch += 1
-
-    @staticmethod
-    def _vmax(stt, like):
-        """amsgrad: the running maximum of the second moment, a flat twin of `v` (created on first use)"""
-        if "vmax" not in stt:
-            stt["vmax"] = torch.zeros_like(like)
-        return stt["vmax"]
-
-    def _arena_state(self, a):
-        stt = self._flat.get(id(a))
-        if stt is None:
-            stt = dict(m=torch.zeros_like(a.P), v=torch.zeros_like(a.P))
-            self._flat[id(a)] = stt
-        return stt
-
-    def _loose_state(self, p):
-        stt = self._loose.get(id(p))
-        if stt is None:
-            stt = dict(m=torch.zeros(p.numel(), device=p.device), v=torch.zeros(p.numel(), device=p.device))
-            self._loose[id(p)] = stt
-        return stt
-
-    # ---- checkpointing: torch.optim.Adam's state_dict layout, so either side resumes the other's run ----------
-    def _moments(self, p, create=False, amsgrad=False):
-        """(exp_avg, exp_avg_sq[, max_exp_avg_sq]) of p as tensors of p's logical shape (views of the flat buffers), or None"""
-        a = getattr(p, "_koaf_arena", None)
-        if a is not None and a.valid():
-            if id(a) not in self._flat and not create:
-                return None
-            stt = self._arena_state(a)
-            o, n = a.slot(p)
-            out = (a._view(stt["m"], o, n, p), a._view(stt["v"], o, n, p))
-            return out + (a._view(self._vmax(stt, a.P), o, n, p),) if amsgrad else out
-        if id(p) not in self._loose and not create:
-            return None
-        stt = self._loose_state(p)
-        out = (stt["m"].view(p.shape), stt["v"].view(p.shape))
-        return out + (self._vmax(stt, stt["v"]).view(p.shape),) if amsgrad else out
-
-    def _place_pending(self):
-        """moments loaded by load_state_dict() go to their flat buffers once the parameters' final placement is known
-        (a model adopts its arena at its first forward, which may come after the optimizer state was loaded)"""
-        for g in self.param_groups:
-            for p in g["params"]:
-                mv = self._pending.pop(id(p), None)
-                if mv is None:
-                    continue
-                if not p.is_cuda:
-                    raise RuntimeError("koaf Adam updates HIP-resident parameters only (no CPU fallback)")
-                dst = self._moments(p, create=True, amsgrad=len(mv) > 2)
-                for d, src in zip(dst, mv):
-                    d.copy_(src.to(device=p.device, dtype=torch.float32))
-        self._pending = {}
-
-    def state_dict(self):
-        if self.capturable:
-            self._sync_steps()
-        sd = super().state_dict()            # param_groups with index lists; `state` is kept outside self.state
-        params = [(p, bool(g.get("amsgrad"))) for g in self.param_groups for p in g["params"]]
-        state = {}
-        for idx, (p, ams) in enumerate(params):
-            n = self._steps.get(id(p), 0)
-            mv = self._pending.get(id(p)) or (self._moments(p, amsgrad=ams) if n else None)   # loaded but not yet placed / live
-            if mv is None:
-                continue                      # never updated (no gradient so far): torch has no entry either
-            state[idx] = dict(step=torch.tensor(float(n)), exp_avg=mv[0].detach().to("cpu").contiguous().clone(),
-                              exp_avg_sq=mv[1].detach().to("cpu").contiguous().clone())
-            if len(mv) > 2:
-                state[idx]["max_exp_avg_sq"] = mv[2].detach().to("cpu").contiguous().clone()
-        sd["state"] = state
-        return sd
-
-    @torch.no_grad()
-    def load_state_dict(self, state_dict):
-        groups = state_dict["param_groups"]
-        super().load_state_dict(dict(state={}, param_groups=groups))
-        params = [p for g in self.param_groups for p in g["params"]]
-        ids = [i for g in groups for i in g["params"]]
-        if len(ids) != len(params):
-            raise ValueError("loaded state dict has a different number of parameters")
-        self._steps, self._pending = {}, {}
-        if self.capturable and state_dict["state"]:
-            counts = {int(round(float(st["step"]))) for st in state_dict["state"].values()}
-            if len(counts) != 1:
-                raise ValueError("capturable Adam keeps one update count for all parameters; the loaded state has several")
-            self._resume_step = counts.pop()         # (device counters created later start here)
-            for d in self._dev.values():
-                d["step"].fill_(self._resume_step)
-        for stt in list(self._flat.values()) + list(self._loose.values()):
-            stt["m"].zero_()
-            stt["v"].zero_()
-            if "vmax" in stt:
-                stt["vmax"].zero_()
-        for key, st in state_dict["state"].items():
-            p = params[ids.index(key)] if key in ids else None
-            if p is None:
-                raise KeyError(f"optimizer state for unknown parameter index {key}")
-            if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                raise ValueError(f"optimizer state shape {tuple(st['exp_avg'].shape)} != parameter shape {tuple(p.shape)}")
-            self._pending[id(p)] = (st["exp_avg"].detach().clone(), st["exp_avg_sq"].detach().clone())
-            if "max_exp_avg_sq" in st:
-                self._pending[id(p)] += (st["max_exp_avg_sq"].detach().clone(),)
-            self._steps[id(p)] = int(round(float(st["step"])))
-
-    def _step_loose(self, p, lr, b1, b2, eps, wd, ams=False):
-        if not p.is_cuda:
-            raise RuntimeError("koaf Adam updates HIP-resident parameters only (no CPU fallback)")
-        stt = self._loose_state(p)
-        n = self._steps.get(id(p), 0) + 1
-        self._steps[id(p)] = n
-        pc = p.data.contiguous().view(-1)
-        g = p.grad.contiguous().view(-1)
-        ops.adam_step(pc, g, stt["m"], stt["v"], pc.numel(), lr, b1, b2, eps, wd, n, self._ADAMW,
-                      vmax=self._vmax(stt, stt["v"]) if ams else None)
-        if pc.data_ptr() != p.data.data_ptr():
-            p.data.copy_(pc.view_as(p.data))
-
-
-class AdamW(Adam):
-    _ADAMW = True
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, capturable=False):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
-                         capturable=capturable)
-
-
-class _FlatStateOptimizer(_ArenaOptimizer):
-    """SGD / RMSprop: state buffers the size of the arena, named with torch's state_dict keys; one launch per contiguous run
-    of parameters with a gradient.  A subclass names the buffers a group uses (`_state_names`) and launches its kernel
-    (`_launch`); everything else -- arena grouping, loose parameters, captured steps, checkpoint layout -- is here."""
-    _NHYPER = 2          # koaf_optim_hyper: {lr, first}
-    _HAS_STEP = False    # torch's per-parameter state carries a `step` entry
-    _USES_FIRST = False  # the first update of a parameter differs from the later ones (SGD's momentum buffer starts as the gradient)
-
-    def _init_flat(self, capturable, differentiable):
-        if differentiable:
-            raise ValueError(f"koaf {self._NAME}: differentiable=True is not supported (the update runs in a HIP kernel outside autograd)")
-        self.capturable = bool(capturable)
-        self._dev = {}       # capturable: (id(arena), id(group)) -> device step count / lr / hyper (see _ArenaOptimizer._dev_state)
-        self._flat = {}      # id(arena) -> {state name: flat buffer like arena.P}
-        self._loose = {}     # id(param) -> {state name: flat buffer} for parameters outside any arena
-        self._steps = {}     # id(param) -> number of updates it has received
-        self._pending = {}   # id(param) -> {state name: tensor} loaded before the parameter moved into its arena
-
-    def _state_names(self, group):
-        raise NotImplementedError
-
-    def _launch(self, group, p, g, st, n, first, hyper):
-        raise NotImplementedError
-
     @staticmethod
     def _bufs(stt, names, like):
         """the flat state buffers `names` of one arena / loose parameter (created zeroed on first use), sized like `like`"""
@@ -316,19 +131,20 @@ class _FlatStateOptimizer(_ArenaOptimizer):
                     if not torch.cuda.is_current_stream_capturing():
                         self.sync_hyper()
                     d["params"].update(id(p) for p in plist)
-                    ops.optim_hyper(d["step"], d["lr"], d["hyper"])
-                    runs = {False: plist}    # (one shared count: `first` comes from the device)
+                    self._hyper(group, d)
+                    runs = {False: plist}    # (one shared count: what depends on it comes from the device)
                 else:
-                    # one fused launch per contiguous run of parameters that are all at their first update, or all past it
-                    # (for the reference models: every trained parameter receives a gradient from the first step on)
+                    # one fused launch per contiguous run of parameters whose update counts share a key (SGD: all at their
+                    # first update, or all past it; Adam: one count).  For the reference models: every trained parameter
+                    # receives a gradient from the first step on
                     d, runs = None, {}
                     for p in plist:
                         n = self._steps.get(id(p), 0) + 1
                         self._steps[id(p)] = n
-                        runs.setdefault(self._USES_FIRST and n == 1, []).append(p)
-                for first, ps in runs.items():
+                        runs.setdefault(self._run_key(n), []).append(p)
+                for key, ps in runs.items():
                     for lo, hi in a.active_ranges(ps):
-                        self._launch(group, a.P[lo:hi], a.G[lo:hi], {k: stt[k][lo:hi] for k in names}, hi - lo, first,
+                        self._launch(group, a.P[lo:hi], a.G[lo:hi], {k: stt[k][lo:hi] for k in names}, hi - lo, key,
                                      d["hyper"] if d else None)
                 a.epoch += 1             # the weights changed under the arena's plane images (arena.ensure_planes)
         return loss
@@ -340,7 +156,7 @@ class _FlatStateOptimizer(_ArenaOptimizer):
         self._steps[id(p)] = n
         pc = p.data.contiguous().view(-1)
         g = p.grad.contiguous().view(-1)
-        self._launch(group, pc, g, stt, pc.numel(), n == 1, None)
+        self._launch(group, pc, g, stt, pc.numel(), self._run_key(n), None)
         if pc.data_ptr() != p.data.data_ptr():
             p.data.copy_(pc.view_as(p.data))
 
@@ -426,7 +242,46 @@ class _FlatStateOptimizer(_ArenaOptimizer):
                 d["step"].fill_(self._resume_step)
 
 
-class SGD(_FlatStateOptimizer):
+class Adam(_ArenaOptimizer):
+    _NAME = "Adam"
+    _NHYPER = 3          # koaf_adam_hyper: {lr, lr / (1 - b1^step), sqrt(1 - b2^step)}
+    _HAS_STEP = True
+    _ADAMW = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, capturable=False):
+        """capturable (as in torch.optim.Adam): learning rate and step count live in device memory (koaf_adam_hyper), so that
+        step() can be captured into a HIP graph and still advance on every replay (run.GraphedTrainStep); arena parameters
+        only, one shared update count (every trained parameter receives a gradient every step)."""
+        if lr < 0 or eps < 0 or weight_decay < 0:
+            raise ValueError("invalid Adam hyper-parameter")
+        self._init_flat(capturable)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad)))
+
+    def _state_names(self, group):
+        return ("exp_avg", "exp_avg_sq") + (("max_exp_avg_sq",) if group.get("amsgrad") else ())
+
+    def _run_key(self, n):
+        return n             # the bias correction depends on the parameter's own update count
+
+    def _hyper(self, group, d):
+        b1, b2 = group["betas"]
+        ops.adam_hyper(d["step"], d["lr"], b1, b2, d["hyper"])
+
+    def _launch(self, group, p, g, st, n, key, hyper):
+        b1, b2 = group["betas"]
+        ops.adam_step(p, g, st["exp_avg"], st["exp_avg_sq"], n, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                      1 if hyper is not None else key, self._ADAMW, hyper=hyper, vmax=st.get("max_exp_avg_sq"))
+
+
+class AdamW(Adam):
+    _ADAMW = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, capturable=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad,
+                         capturable=capturable)
+
+
+class SGD(_ArenaOptimizer):
     """torch.optim.SGD (its constructor signature and defaults, its single-tensor update rule, its state_dict layout) on
     koaf_sgd_step.  foreach / fused are accepted and ignored: the update is always one fused pass per contiguous arena run.
     capturable (as on Adam): learning rate and step count live in device memory, for run.GraphedTrainStep; arena parameters
@@ -435,7 +290,6 @@ class SGD(_FlatStateOptimizer):
     which is torch's result only for dampening == 0.  Every trained parameter of the registry models receives a gradient from
     the first step on; for anything else with a dampening, use capturable=False (per-parameter flags)."""
     _NAME = "SGD"
-    _USES_FIRST = True
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
                  foreach=None, differentiable=False, fused=None, capturable=False):
@@ -455,12 +309,15 @@ class SGD(_FlatStateOptimizer):
     def _state_names(self, group):
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
 
+    def _run_key(self, n):
+        return n == 1        # the first update differs from the later ones: the momentum buffer starts as the gradient
+
     def _launch(self, group, p, g, st, n, first, hyper):
         ops.sgd_step(p, g, st.get("momentum_buffer"), n, group["lr"], momentum=group["momentum"], dampening=group["dampening"],
                      wd=group["weight_decay"], nesterov=group["nesterov"], maximize=group["maximize"], first=first, hyper=hyper)
 
 
-class RMSprop(_FlatStateOptimizer):
+class RMSprop(_ArenaOptimizer):
     """torch.optim.RMSprop (constructor signature and defaults, single-tensor update rule, state_dict layout) on
     koaf_rmsprop_step; foreach is accepted and ignored; capturable as on Adam / SGD."""
     _NAME = "RMSprop"
@@ -486,7 +343,7 @@ class RMSprop(_FlatStateOptimizer):
     def _state_names(self, group):
         return ("square_avg",) + (("momentum_buffer",) if group["momentum"] > 0 else ()) + (("grad_avg",) if group["centered"] else ())
 
-    def _launch(self, group, p, g, st, n, first, hyper):
+    def _launch(self, group, p, g, st, n, key, hyper):
         ops.rmsprop_step(p, g, st["square_avg"], n, group["lr"], alpha=group["alpha"], eps=group["eps"], wd=group["weight_decay"],
                          momentum=group["momentum"], gavg=st.get("grad_avg"), buf=st.get("momentum_buffer"),
                          maximize=group["maximize"], hyper=hyper)

@@ -1,12 +1,13 @@
-"""optimizer step time of the registry's SGD / RMSprop on the flagship model's parameter arena (GPU box):
+"""optimizer step time of the registry's SGD / RMSprop / Adam on the flagship model's parameter arena (GPU box):
     python scripts/bench_optim_step.py [--steps 200] [--block 25] [--warmup 10] [--out result.json]
 Times ONE optimizer.step() -- device events around the step only, no forward / backward -- for XR1MR2C1CnnTrf at its native
 sizes (every parameter holds a gradient: views of the arena's flat gradient buffer), for
-    native:  dict_optimizers["SGD"](momentum=0.9) / dict_optimizers["RMSprop"]()      (koaf_sgd_step / koaf_rmsprop_step)
-    torch:   torch.optim.SGD(momentum=0.9) / torch.optim.RMSprop()                    (what those keys held before)
+    native:  dict_optimizers["SGD"](momentum=0.9) / ["RMSprop"]() / ["Adam"]()        (koaf_sgd_step / koaf_rmsprop_step / koaf_adam_step)
+    torch:   torch.optim.SGD(momentum=0.9) / torch.optim.RMSprop() / torch.optim.Adam()
 on the SAME arena-backed parameters, in alternating blocks of `--block` steps on one device, `--steps` timed steps each.
-Prints per optimizer the median step time of both, the spread of the block medians, and the bytes-moved floor (5 x 4 B per
-element for both: p, g and one state buffer read, p and the state written) at the achievable HBM rate, 6.3 TB/s."""
+Prints per optimizer the median step time of both, the spread of the block medians, and the bytes-moved floor (SGD, RMSprop:
+5 x 4 B per element -- p, g and one state buffer read, p and the state written; Adam: 7 x 4 B -- p, g, m, v read, p, m, v
+written) at the achievable HBM rate, 6.3 TB/s."""
 import argparse, json, statistics, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -38,7 +39,8 @@ for p in params:
     p.grad = p._koaf_grad
 n_elem = sum(hi - lo for lo, hi in a.active_ranges(params))
 # (tiny learning rates: 2 x (warmup + steps) updates must leave the weights where they are, whatever the rule)
-CASES = {"SGD": (dict(lr=1e-7, momentum=0.9), 5), "RMSprop": (dict(lr=1e-9), 5)}      # name -> (arguments, fp32 words moved per element)
+CASES = {"SGD": (dict(lr=1e-7, momentum=0.9), 5), "RMSprop": (dict(lr=1e-9), 5),
+         "Adam": (dict(lr=1e-9), 7)}      # name -> (arguments, fp32 words moved per element)
 
 
 def time_block(opt, k):

@@ -74,7 +74,7 @@ def test_constructor_validation_matches_torch():
     assert (g["lr"], g["alpha"], g["eps"], g["weight_decay"], g["momentum"], g["centered"]) == (1e-2, 0.99, 1e-8, 0, 0, False)
 
 
-@pytest.mark.parametrize("name", ["SGD", "RMSprop"])
+@pytest.mark.parametrize("name", ["SGD", "Adam", "AdamW", "RMSprop"])
 def test_cpu_parameter_raises(name):
     from oaprogressionmmf_amd.various import dict_optimizers
     p = torch.nn.Parameter(torch.zeros(5))

@@ -1,7 +1,8 @@
 """GPU: the native SGD / RMSprop / BCE registry entries against the torch classes the reference registers
 (koafusion/various/_optimizers.py:47-52, _losses.py:111-117), which run on the CPU here as the reference.
  * kernels: four steps of fixed gradients over an odd length (vector body + scalar tail), every option
- * optimizer classes on a registry model: only the update rule is compared (torch is fed the device run's gradients)
+ * optimizer classes on a registry model, all four keys (Adam / AdamW share the base class of the other two): only the update
+   rule is compared (torch is fed the device run's gradients)
  * resume through save_train_state / load_train_state, into a fresh native instance and into torch.optim
  * captured steps (run.GraphedTrainStep) bit-identical to eager ones, with a scheduler step between replays
  * BCELoss / BCEWithLogitsLoss against torch in float64: loss, gradient, options, the grid form's determinism
@@ -114,7 +115,10 @@ def test_device_step_state_drives_lr_and_first(dev):
 
 # ---- optimizer classes on a registry model ------------------------------------------------------------------------------------
 OPTS = {"SGD": dict(lr=1e-3, momentum=0.9, weight_decay=1e-4),
-        "RMSprop": dict(lr=1e-5, momentum=0.5, centered=True, weight_decay=1e-4)}    # (small: RMSprop's first steps are ~10 lr per weight)
+        "RMSprop": dict(lr=1e-5, momentum=0.5, centered=True, weight_decay=1e-4),    # (small: RMSprop's first steps are ~10 lr per weight)
+        "Adam": dict(lr=1e-4, weight_decay=1e-4),
+        "AdamW": dict(lr=1e-4, weight_decay=1e-2),
+        "Adam-amsgrad": dict(lr=1e-4, amsgrad=True)}                                 # (the class is the part before the dash)
 
 
 def _small_case(dev, seed):
@@ -137,9 +141,10 @@ def _hand_grads(cpu_params, m):
         cp.grad = None if p.grad is None else p.grad.detach().cpu().contiguous().clone()
 
 
-@pytest.mark.parametrize("name", ["SGD", "RMSprop"])
+@pytest.mark.parametrize("name", ["SGD", "RMSprop", "Adam", "AdamW", "Adam-amsgrad"])
 def test_optimizer_class_on_a_registry_model(dev, name):
     """three steps: the update rule alone against torch.optim on CPU copies fed the device run's gradients"""
+    cls = name.split("-")[0]
     from oaprogressionmmf_amd.arena import get_arena
     from oaprogressionmmf_amd.various import dict_losses, dict_optimizers
     # (the fusion model with two MRI branches: the `mlp_head0` tensors of its cls-less aggregators never receive a gradient)
@@ -148,11 +153,11 @@ def test_optimizer_class_on_a_registry_model(dev, name):
     y = t(P.make_target("target", 2, 9)).to(dev)
     loss_fn = dict_losses["FocalLoss"](reduction="mean", gamma=2.0, num_classes=2)
     m = build(cfg, dev).train()
-    opt = dict_optimizers[name](m.parameters(), **OPTS[name])
+    opt = dict_optimizers[cls](m.parameters(), **OPTS[name])
     assert type(opt).__module__.startswith("oaprogressionmmf_amd")
     cpu_params = [torch.nn.Parameter(p.detach().cpu().contiguous().clone()) for p in m.parameters()]
     start = [cp.detach().clone() for cp in cpu_params]
-    ref = getattr(torch.optim, name)(cpu_params, **OPTS[name])
+    ref = getattr(torch.optim, cls)(cpu_params, **OPTS[name])
     logits0 = _backward(m, opt, loss_fn, xs, y)
     arena = get_arena(m)
     epoch0 = arena.epoch
@@ -171,7 +176,7 @@ def test_optimizer_class_on_a_registry_model(dev, name):
             continue
         e = rel(p.detach().cpu().numpy(), cp.detach().numpy())
         worst = max(worst, e)
-        assert e < 1e-6, f"{name}: {k} differs from torch.optim.{name} by {e:.3e}"
+        assert e < 1e-6, f"{name}: {k} differs from torch.optim.{cls} by {e:.3e}"
         moved += int(not torch.equal(p.detach().cpu(), p0))
     print(f"{name}: worst parameter rel err {worst:.3e}; {moved} tensors moved, {idle} without gradient")
     assert moved > 0 and idle > 0
@@ -268,7 +273,7 @@ def test_graphed_train_step_replay_is_bit_identical_to_eager(dev, name, kw, call
         assert torch.equal(p0[k], p1[k]), k
 
 
-@pytest.mark.parametrize("name", ["SGD", "RMSprop"])
+@pytest.mark.parametrize("name", ["SGD", "Adam", "AdamW", "RMSprop"])
 def test_capturable_refuses_a_loose_parameter(dev, name):
     from oaprogressionmmf_amd.various import dict_optimizers
     p = torch.nn.Parameter(torch.zeros(8, device=dev))
