@@ -513,6 +513,23 @@ int koaf_maxpool_bwd(const float* dy, const uint8_t* argmax, float* da, int32_t 
 int koaf_gap_fwd(const float* y, float* out, int32_t N, int32_t HW, int32_t C, int32_t act16, void* stream);
 int koaf_gap_bwd(const float* dout, float* dy, int32_t N, int32_t HW, int32_t C, void* stream);
 
+/* ---- Class-activation maps of the slice-wise trunks (koaf_cam.hip; not in the reference) -------
+ * cam[n][p] = sum_c A[n][p][c] * w[n][c], clamped at 0 when `relu`; A [N][HW][C] the trunk's NHWC feature map (fp32, or bf16
+ * when act16: widened on load, exact), w [N][C] fp32 (Grad-CAM: the gradient of the logit with respect to the pooled token,
+ * over HW).  img_sum[n] = sum_p of the stored cam[n][p]; img_max[n] = max_p |cam[n][p]|.  One block per image, one wave per
+ * pixel row at a time; every reduction is a fixed-order tree (no atomics): run-to-run identical bits.  A NaN in a row gives a
+ * NaN in that pixel, in img_sum[n] and in img_max[n] (integer maximum over the magnitude bits).  C % 4 == 0, C <= 16384. */
+int koaf_cam(const float* A, const float* w, float* cam, float* img_sum, float* img_max, int32_t N, int32_t HW, int32_t C,
+             int32_t relu, int32_t act16, void* stream);
+/* image n = b*K + k of cam [B*K][h][w] resized to H x W (torch's align_corners=False bilinear rule, as koaf_resize), divided by a
+ * maximum and written to out[b*sb + k*sk + i*si + j*sj] (strides in elements, all > 0): resize, normalise and the unfold into the
+ * layout the model received in one write pass.  normalize 0: none; 1: by the largest img_max among the sample's K images;
+ * 2: by the image's own img_max.  A maximum of 0 writes zeros, a non-finite one NaN for everything it scales.  Consecutive
+ * lanes walk the unit-stride axis of out: columns (sj == 1) or slices (sk == 1, the (B,1,R,C,S) volumes: whole output rows from
+ * a source row staged in LDS, where its w * K floats fit).  K <= 8192 and 8 (H + W) + 4 K <= 65536 (taps and scales sit in LDS). */
+int koaf_cam_upsample(const float* cam, const float* img_max, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t H,
+                      int32_t W, int64_t sb, int64_t sk, int64_t si, int64_t sj, int32_t normalize, void* stream);
+
 /* ---- Input plumbing -------------------------------------------------------------------------- */
 /* "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209-210): x [B,R,C,S] -> out [B*S,R,C] */
 int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,

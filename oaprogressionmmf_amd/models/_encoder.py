@@ -500,6 +500,11 @@ class EncoderFn(torch.autograd.Function):
             y, Hc, Wc = y_out, Ho, Wo
             stages_saved.append(sv)
         C = y.shape[-1]
+        if trunk.keep_features:
+            # class-activation maps (run.gradcam): the last stage's output as stored, read later on the caller's stream
+            if CALLER_STREAM is not None:
+                y.record_stream(CALLER_STREAM)
+            trunk.features = (y, N, Hc, Wc, C)
         if st["gap"]:
             out = ops.gap_fwd(y, N, Hc * Wc, C).view(N, C, 1, 1)
         else:
@@ -715,6 +720,10 @@ class KoafTrunk(nn.Sequential):
     tensors saved for backward; arithmetic, statistics, gradients and parameters stay fp32).  Set per model by the config key
     `activation_storage: bf16` (models/_common.apply_activation_storage)."""
     act_dtype = torch.float32
+    # set (per instance, for one call) by run.gradcam: the forward leaves `features` = (y, N, h, w, C), the last stage's NHWC
+    # output as stored (bf16 in the bf16 storage mode), in front of the GAP / the NCHW view
+    keep_features = False
+    features = None
 
     def _koaf_layout(self):
         lay = self.__dict__.get("_koaf_lay")

@@ -626,6 +626,44 @@ def gap_bwd(dout, N, HW, C):
 
 
 # ------------------------------------------------------------------------------------------------
+# class-activation maps
+# ------------------------------------------------------------------------------------------------
+def cam(A, w, N, HW, C, relu=True):
+    """cam[n][p] = sum_c A[n][p][c] * w[n][c] (clamped at 0 with `relu`) of an NHWC feature map A (fp32 or bf16 storage) and fp32
+    weights w [N, C] -> (cam [N, HW], img_sum [N] = sum_p cam, img_max [N] = max_p |cam|), all fp32 (koaf_cam: fixed order)"""
+    if A.dtype not in (torch.float32, torch.bfloat16) or w.dtype != torch.float32:
+        raise KoafError(f"cam: an fp32 / bf16 feature map and fp32 weights, got {A.dtype} and {w.dtype}")
+    if not (A.is_contiguous() and w.is_contiguous()) or A.numel() != N * HW * C or w.numel() != N * C:
+        raise KoafError(f"cam: contiguous A [{N}, {HW}, {C}] and w [{N}, {C}], got {tuple(A.shape)} and {tuple(w.shape)}")
+    out = torch.empty((N, HW), device=A.device, dtype=torch.float32)
+    stat = torch.empty((2, N), device=A.device, dtype=torch.float32)
+    check(lib().koaf_cam(_ptr(A), _ptr(w), _ptr(out), _ptr(stat[0]), _ptr(stat[1]), N, HW, C, 1 if relu else 0, _a16(A), _stream()),
+          "cam")
+    return out, stat[0], stat[1]
+
+
+CAM_NORMALIZE = {None: 0, "sample": 1, "image": 2}
+
+
+def cam_upsample(cam, img_max, out, B, K, h, w, H, W, strides, normalize=None):
+    """image b*K + k of cam [B*K, h, w] resized to H x W (bilinear, align_corners=False), divided by a maximum (normalize: None,
+    "sample" = the largest img_max of the sample's K images, "image" = its own) and written to out[b*sb + k*sk + i*si + j*sj],
+    strides = (sb, sk, si, sj) in elements (koaf_cam_upsample: one write pass).  Elements of `out` no (b, k, i, j) reaches stay."""
+    if normalize not in CAM_NORMALIZE:
+        raise ValueError(f"Unknown normalize: {normalize}")
+    if cam.dtype != torch.float32 or out.dtype != torch.float32 or not (cam.is_contiguous() and out.is_contiguous()):
+        raise KoafError("cam_upsample: contiguous fp32 tensors only")
+    if cam.numel() != B * K * h * w or (img_max is not None and (img_max.numel() != B * K or not img_max.is_contiguous())):
+        raise KoafError(f"cam_upsample: cam [{B * K}, {h}, {w}] and img_max [{B * K}], got {tuple(cam.shape)}")
+    sb, sk, si, sj = (int(s) for s in strides)
+    if min(sb, sk, si, sj) <= 0 or (B - 1) * sb + (K - 1) * sk + (H - 1) * si + (W - 1) * sj >= out.numel():
+        raise KoafError(f"cam_upsample: strides {(sb, sk, si, sj)} leave the {out.numel()} elements of out")
+    check(lib().koaf_cam_upsample(_ptr(cam), _ptr(img_max), _ptr(out), B, K, h, w, H, W, sb, sk, si, sj, CAM_NORMALIZE[normalize],
+                                  _stream()), "cam_upsample")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # input plumbing
 # ------------------------------------------------------------------------------------------------
 def slice_fold(x, B, R, Cc, S):

@@ -6,7 +6,9 @@ from ._graph import GraphedPredictor, GraphedTrainStep
 from ._accum import GradientFold, micro_batch_weights, train_step_accum
 from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ablation_percent, input_gradients,
                        saliency_maps)
+from ._gradcam import GradCam, cam_strides, gradcam
 
 __all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
-           "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum"]
+           "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum", "GradCam",
+           "cam_strides", "gradcam"]

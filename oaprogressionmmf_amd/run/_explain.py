@@ -10,7 +10,8 @@ Here the M + 1 forwards run on the HIP path and only the (B, M) differences leav
 Not in the reference: input gradients.  input_gradients / saliency_maps return d logit[b, target_b] / d x_m for every input
 (one forward and one backward through the HIP path, the trunks' data gradient down to the image included), and
 explain_epoch(explain_fn="input_x_grad") accumulates the per-modality totals sum(x_m * grad_m) -- the first-order estimate of
-what the ablation measures with M + 1 forwards."""
+what the ablation measures with M + 1 forwards.  Class-activation maps (run/_gradcam.py): explain_epoch(explain_fn="gradcam")
+accumulates the per-slice map sums and hands the Grad-CAM volumes to the sink."""
 from collections import defaultdict
 
 import numpy as np
@@ -99,8 +100,12 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
     explain_fn="input_x_grad" (not in the reference): the same dict with ixg_attrs = sum(x_m * grad_m) per modality and
     ixg_percent (ablation_percent of those) instead, for one forward and one backward per batch.  The gradient x input maps
     themselves (device tensors shaped like the inputs the model receives, i.e. after `downscale`) go to
-    sink(exam_knee_ids, modals, maps) when a sink is given, and never into the returned lists."""
-    if explain_fn not in ("modal_abl", "input_x_grad"):
+    sink(exam_knee_ids, modals, maps) when a sink is given, and never into the returned lists.
+    explain_fn="gradcam" (not in the reference): exam_knee_id, target, modal_names and gradcam_slice_scores -- per sample, one list
+    per modality of the K per-slice sums of the un-normalised ReLU'd low-resolution Grad-CAM map ([] for a modality without an
+    encoder trunk).  The maps (run.gradcam defaults: normalised per sample, shaped like the inputs; None for a trunk-less
+    modality) go to the sink in the same way."""
+    if explain_fn not in ("modal_abl", "input_x_grad", "gradcam"):
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
     field = "modal_abl" if explain_fn == "modal_abl" else "ixg"
     acc = defaultdict(list)
@@ -110,6 +115,18 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
         ys = torch.as_tensor(batch["target"])
         with torch.no_grad():
             xs = tuple(downscale_inputs(xs, downscale))
+        if explain_fn == "gradcam":
+            from ._gradcam import gradcam
+            cams = gradcam(model, xs, ys.squeeze())
+            scores = [c.slice_scores.to("cpu").numpy().tolist() if c is not None else None for c in cams]
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, tuple(c.map if c is not None else None for c in cams))
+            nb = xs[0].shape[0]
+            acc["exam_knee_id"].extend(batch[("-", "exam_knee_id")])
+            acc["target"].extend(ys.to("cpu").numpy().tolist())
+            acc["modal_names"].extend([modals, ] * nb)
+            acc["gradcam_slice_scores"].extend([[s[b] if s is not None else [] for s in scores] for b in range(nb)])
+            continue
         if explain_fn == "modal_abl":
             attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
         else:
