@@ -530,6 +530,34 @@ int koaf_cam(const float* A, const float* w, float* cam, float* img_sum, float* 
 int koaf_cam_upsample(const float* cam, const float* img_max, float* out, int32_t B, int32_t K, int32_t h, int32_t w, int32_t H,
                       int32_t W, int64_t sb, int64_t sk, int64_t si, int64_t sj, int32_t normalize, void* stream);
 
+/* ---- Path attributions over the inputs: integrated gradients, SmoothGrad (koaf_attr.hip; not in the reference) -------
+ * All tensors are contiguous fp32 rows [B][n], any n >= 1; rows need not be 16-byte aligned (16-byte accesses where n % 4 == 0
+ * and the pointers are aligned, one element per lane otherwise).  Element-wise, no atomics: the bits do not depend on the grid.
+ * No operation is fused: every difference, product and sum below is rounded to fp32 on its own, in the order written, so that
+ * numpy's fp32 restates both kernels bit for bit.  1 <= J <= KOAF_ATTR_MAX_J (alpha and the generator keys sit in LDS).
+ *
+ * koaf_path_points  out[j][b][i] = (bs + alpha[j] * (x[b][i] - bs)) + sigma_b * z(seed, draw0 + j, b, i),  j in [0, J)
+ *   bs = base[b][i], or base_value when base is NULL;  alpha: device [J];  out: [J][B][n];  x and base are read once for all J.
+ *   sigma_b = noise_level * (mm[b][1] - mm[b][0]), mm [B][2] as koaf_minmax leaves it.  mm NULL or noise_level == 0: no noise
+ *   term at all (nothing is drawn, nothing added).  B <= 65535; draw0 >= 0, draw0 + J <= 2^31.
+ *   z: a standard normal, a function of (seed, draw index d = draw0 + j, b, i) only -- not of J, B, n, the grid, or how the
+ *   draws are split over calls.  With mix64(v): v += 0x9E3779B97F4A7C15; v = (v ^ v >> 30) * 0xBF58476D1CE4E5B9;
+ *   v = (v ^ v >> 27) * 0x94D049BB133111EB; return v ^ v >> 31  (64-bit wrap-around; the dropout kernels' hash):
+ *     key = mix64(seed ^ mix64(d << 32 | b));   h = mix64(key ^ mix64(i >> 1))          one hash per PAIR of elements
+ *     u1 = ((h >> 40) + 1) / 2^24  in (0, 1];   u2 = ((h >> 16) & 0xFFFFFF) / 2^24  in [0, 1)
+ *     r = sqrt(-2 ln u1);   z = r cos(2 pi u2) for even i,  r sin(2 pi u2) for odd i     (Box-Muller)
+ *   evaluated in fp32 as sqrtf(-2 * logf(u1)) and sincospif(2 u2) (2 u2 is exact; the pi-scaled functions need no argument
+ *   reduction).  |z| <= sqrt(2 ln 2^24) = 5.77.
+ * koaf_attr_fold  s = first ? +0 : acc[b][i];  for j = 0 .. J-1 in order: s = s + w[j] * f(g[j][b][i]);  f(v) = v, or v * v when
+ *   `square`;  g: [J][B][n], w: device [J].  acc[b][i] = s, or, with `finish`, s * (x[b][i] - bs) (bs as above): the
+ *   integrated-gradients map, written by the last chunk's call without another pass.  Without `finish`, x and base are not read
+ *   (and may be NULL). */
+#define KOAF_ATTR_MAX_J 64
+int koaf_path_points(const float* x, const float* base, float base_value, const float* alpha, float* out, int32_t J, int32_t B,
+                     int64_t n, const float* mm, float noise_level, uint64_t seed, int64_t draw0, void* stream);
+int koaf_attr_fold(float* acc, const float* g, const float* w, const float* x, const float* base, float base_value, int32_t J,
+                   int32_t B, int64_t n, int32_t square, int32_t first, int32_t finish, void* stream);
+
 /* ---- Input plumbing -------------------------------------------------------------------------- */
 /* "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209-210): x [B,R,C,S] -> out [B*S,R,C] */
 int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,

@@ -89,6 +89,14 @@ __device__ __forceinline__ void block_amax_raise_bits(unsigned bits, float* slot
 }
 __device__ __forceinline__ void block_amax_raise(float v, float* slot) { block_amax_raise_bits(koaf_absbits(v), slot); }
 
+// The hash of the counter-based generators (dropout masks: koaf_elem.hip; Gaussian draws: koaf_attr.hip): the splitmix64 step.
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---- numerics status words (koaf.h koaf_set_status_buffer): device uint32[4] registered by the host, or NULL -------------
 //   [0] activation-operand elements / tiles that left the fp16 range of the fixed activation scale (clamped) or were not finite
 //   [1] non-finite operand scales (a NaN / Inf in a weight or gradient tensor) and non-finite BatchNorm coefficients

@@ -909,12 +909,7 @@ __global__ void __launch_bounds__(256) pointwise_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (mix64, the counter-based generator's hash: koaf_common.h -- shared with koaf_attr.hip)
 // `epoch` (nullable): a device-resident step counter folded into the seed, so that a HIP-graph replay of a captured step
 // (whose `seed` argument is frozen) still draws fresh masks every step; forward and backward of one step read the same value
 __device__ __forceinline__ uint64_t step_seed(uint64_t seed, const int64_t* epoch) {

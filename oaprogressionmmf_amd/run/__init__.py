@@ -7,8 +7,9 @@ from ._accum import GradientFold, micro_batch_weights, train_step_accum
 from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ablation_percent, input_gradients,
                        saliency_maps)
 from ._gradcam import GradCam, cam_strides, gradcam
+from ._attr import attribution_totals, integrated_gradients, quadrature, smoothgrad
 
 __all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
            "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum", "GradCam",
-           "cam_strides", "gradcam"]
+           "cam_strides", "gradcam", "attribution_totals", "integrated_gradients", "quadrature", "smoothgrad"]

@@ -11,7 +11,9 @@ Not in the reference: input gradients.  input_gradients / saliency_maps return d
 (one forward and one backward through the HIP path, the trunks' data gradient down to the image included), and
 explain_epoch(explain_fn="input_x_grad") accumulates the per-modality totals sum(x_m * grad_m) -- the first-order estimate of
 what the ablation measures with M + 1 forwards.  Class-activation maps (run/_gradcam.py): explain_epoch(explain_fn="gradcam")
-accumulates the per-slice map sums and hands the Grad-CAM volumes to the sink."""
+accumulates the per-slice map sums and hands the Grad-CAM volumes to the sink.  Path attributions (run/_attr.py):
+explain_epoch(explain_fn="integrated_gradients" | "smoothgrad") accumulates the per-modality totals of the maps and hands the
+maps to the sink."""
 from collections import defaultdict
 
 import numpy as np
@@ -94,7 +96,10 @@ def ablation_percent(attrs):
     return np.round(np.abs(t.numpy()) * 100., decimals=3)
 
 
-def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None):
+EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad")
+
+
+def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None, explain_kwargs=None):
     """One pass of an eval()-mode model over `loader`; returns the reference's accumulator dict: exam_knee_id,
     target, modal_names, modal_abl_attrs, modal_abl_percent (python lists, loader order).
     explain_fn="input_x_grad" (not in the reference): the same dict with ixg_attrs = sum(x_m * grad_m) per modality and
@@ -104,10 +109,19 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
     explain_fn="gradcam" (not in the reference): exam_knee_id, target, modal_names and gradcam_slice_scores -- per sample, one list
     per modality of the K per-slice sums of the un-normalised ReLU'd low-resolution Grad-CAM map ([] for a modality without an
     encoder trunk).  The maps (run.gradcam defaults: normalised per sample, shaped like the inputs; None for a trunk-less
-    modality) go to the sink in the same way."""
-    if explain_fn not in ("modal_abl", "input_x_grad", "gradcam"):
+    modality) go to the sink in the same way.
+    explain_fn="integrated_gradients" (not in the reference): ig_attrs = the per-modality sums of the run.integrated_gradients
+    maps, ig_percent (ablation_percent of those) and ig_delta = the per-sample completeness residual sum_m ig_attrs - (F(x) -
+    F(baseline)).  explain_fn="smoothgrad": sg_attrs = sum(x_m * map_m) of the run.smoothgrad maps and sg_percent.  Both hand
+    their maps to the sink as "input_x_grad" does, and both pass `explain_kwargs` (a dict: n_steps, method, baselines, chunk /
+    n_samples, noise_level, seed, kind, chunk) to the function; the other keys take no keywords."""
+    if explain_fn not in EXPLAIN_FNS:
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
-    field = "modal_abl" if explain_fn == "modal_abl" else "ixg"
+    kwargs = dict(explain_kwargs or {})
+    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad"):
+        raise ValueError(f"explain_fn {explain_fn} takes no explain_kwargs, got {sorted(kwargs)}")
+    kwargs.pop("return_delta", None)
+    field = {"modal_abl": "modal_abl", "integrated_gradients": "ig", "smoothgrad": "sg"}.get(explain_fn, "ixg")
     acc = defaultdict(list)
     modals = list(modals)
     for batch in loader:
@@ -127,8 +141,21 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
             acc["modal_names"].extend([modals, ] * nb)
             acc["gradcam_slice_scores"].extend([[s[b] if s is not None else [] for s in scores] for b in range(nb)])
             continue
+        delta = None
         if explain_fn == "modal_abl":
             attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
+        elif explain_fn == "integrated_gradients":
+            from ._attr import attribution_totals, integrated_gradients
+            maps, delta = integrated_gradients(model, xs, ys.squeeze(), return_delta=True, **kwargs)
+            attrs = attribution_totals(maps).to("cpu")
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, maps)
+        elif explain_fn == "smoothgrad":
+            from ._attr import smoothgrad
+            maps = smoothgrad(model, xs, ys.squeeze(), **kwargs)
+            attrs = input_x_grad_totals(xs, maps).to("cpu")
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, maps)
         else:
             grads = input_gradients(model, xs, ys.squeeze())
             attrs = input_x_grad_totals(xs, grads).to("cpu")
@@ -139,6 +166,8 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
         acc["modal_names"].extend([modals, ] * attrs.shape[0])
         acc[f"{field}_attrs"].extend(attrs.numpy().tolist())
         acc[f"{field}_percent"].extend(ablation_percent(attrs).tolist())
+        if delta is not None:
+            acc["ig_delta"].extend(delta.to("cpu").numpy().tolist())
     return dict(acc)
 
 
@@ -146,7 +175,8 @@ def ensemble_explain_foldw(raw_foldw, prefix="modal_abl"):
     """Inner 1:1 merge of the folds on exam_knee_id (first fold's order; target / modal_names from the first fold),
     per-fold columns modal_abl_attrs__k / modal_abl_percent__k, and modal_abl_percent = fold mean of the per-fold
     per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64).
-    prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad")."""
+    prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad"), "ig" / "sg"
+    for "integrated_gradients" / "smoothgrad"."""
     folds = list(raw_foldw)
     if not folds:
         raise ValueError("no folds to ensemble")
