@@ -711,6 +711,48 @@ int64_t koaf_bce_ws(int64_t n);
 int koaf_bce_loss(const float* x, const float* target, const float* weight, const float* pos_weight, float* loss, float* dx,
                   int64_t n, int32_t C, int32_t from_logits, int32_t reduction, float* ws, void* stream);
 
+/* ---- calc_metrics_v2 / calc_bootstrap on the device (koaf_metrics.hip; various/_metrics_stat_anlys.py:28-216,
+ * _metrics_wissam.py:113-172): ROC-AUC, average precision, prevalence-calibrated average precision, the Youden cutoff and the
+ * confusion counts of n <= KOAF_METRICS_MAX_N binary-labelled scores, for the sample itself and for R bootstrap resamples.
+ * The scores are ranked once; a resample changes only how often a sample counts, so it is a histogram over the rank bins.
+ * Arithmetic contract: ranks, histograms, prefix sums and the Mann-Whitney sum are INTEGER (LDS integer atomics: exact and
+ * order-independent); every fp64 value is a quotient of such integers or a sum of such quotients taken in a fixed order (per
+ * thread in bin order over a contiguous run of bins, then a fixed tree over the 256 threads), without fused multiply-add.  No
+ * floating-point atomics: the same bits from run to run, on any grid.
+ * flag: a device uint32 the caller zeroed; bit 0 = a NaN / Inf score, bit 1 = a label other than 0 / 1, bit 2 = an index of the
+ * index matrix (or a rank of `packed`) outside [0, n), which is skipped, never followed.
+ *
+ * koaf_score_ranks  rank[i] = #{ j : s[j] > s[i] } over s[i] = scores[i * stride] (fp32, or fp64 when f64): tied scores get equal
+ *   ranks, rank 0 is the largest score, and the ranks in use are sklearn's distinct thresholds in descending order.  The
+ *   comparison is made in the scores' own precision (fp64 scores are NOT narrowed: that would merge near-ties).  All-pairs
+ *   counting, the scores tiled through LDS; a sample's count does not depend on the grid.  labels (int32 [n], nullable) and
+ *   packed go together: packed[i] = rank[i] << 1 | (labels[i] == pos_label), the word the two kernels below gather.  rank is
+ *   nullable when packed is given.
+ * koaf_curve_metrics  one block per row of out [rows][8] fp64, rows = R + (with_identity ? 1 : 0).  Row r counts the samples
+ *   idx[r'][0..m) (int32, r' = r - with_identity), the identity row (row 0 when with_identity; idx may be NULL when R == 0)
+ *   counts every sample once.  With (tp_g, fp_g) the positives / negatives of rank bin g, tp / fp their running sums including
+ *   g, P / N the totals:
+ *     out[r] = { P, N,  sum_g fp_g * (2 * tp_before_g + tp_g) / (2 P N),  sum_g (tp_g / P) * (tp / (tp + fp)),
+ *                sum_g (tp_g / P) * (tp / (tp + ratio * fp)),  0, 0, 0 }
+ *   ratio = pi * (1 - pi0) / (pi0 * (1 - pi)), pi = P / (P + N) of the row itself; a term whose denominator is 0 counts 0
+ *   (_metrics_wissam.py:150-157).  That is roc_auc_score (the Mann-Whitney form of its trapezoid sum), average_precision_score
+ *   and average_precision_score_calib(pi0) with the positive class `pos_label` of koaf_score_ranks; P == 0 or N == 0 writes NaN
+ *   for the three metrics and the counts.  m <= KOAF_METRICS_MAX_N: a bin's two 16-bit counters cannot carry.
+ * koaf_point_metrics  one block, the identity resample.  out [9] fp64:
+ *   out[0] the Youden cutoff of sensitivity_specificity_cutoff (:224-254): the threshold of the FIRST maximum of tp / P - fp / N
+ *     over the points roc_curve(drop_intermediate=True) keeps -- the first threshold, the last, and every threshold whose
+ *     (tp_g, fp_g) differs from the next threshold's (a non-zero second difference of tps or of fps) -- behind the leading
+ *     (0, 0, +inf) point.  A score value widened to fp64 (exact), or +inf.
+ *   out[1..5) = tn, fp, fn, tp of the prediction s > thr (compared in fp64), out[5..9) = the same of s >= cutoff (in the scores'
+ *     precision; nothing is predicted positive at +inf).  "Positive" is packed's label bit. */
+#define KOAF_METRICS_MAX_N 16384
+int koaf_score_ranks(const void* scores, int32_t f64, int64_t stride, int32_t n, const int32_t* labels, int32_t pos_label,
+                     int32_t* rank, int32_t* packed, uint32_t* flag, void* stream);
+int koaf_curve_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int32_t R, int32_t m, int32_t with_identity,
+                       double pi0, double* out, uint32_t* flag, void* stream);
+int koaf_point_metrics(const void* scores, int32_t f64, int64_t stride, const int32_t* packed, int32_t n, double thr, double* out,
+                       uint32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

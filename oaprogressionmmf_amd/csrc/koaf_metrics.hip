@@ -1,0 +1,286 @@
+// koaf_metrics.hip -- the validation / evaluation metrics of calc_metrics_v2 (various/_metrics_stat_anlys.py:28-216,
+// _metrics_wissam.py:113-172) on the device, bootstrap included.  The scores are ranked once (all-pairs counting, no sort); a
+// resample then only changes how often each sample counts, so each resample is an integer histogram over the rank bins and one
+// ordered pass over it.  Everything that decides a result is integer arithmetic (LDS integer atomics, integer prefix sums, the
+// Mann-Whitney sum in int64); the fp64 sums run in a fixed order.  No floating-point atomics: run-to-run identical bits.
+#include "koaf_common.h"
+
+namespace {
+
+constexpr int MT_BLOCK = 256;
+constexpr int MT_MAX_N = KOAF_METRICS_MAX_N;
+constexpr int MT_TILE = 2048;            // scores per LDS tile of the rank kernel
+
+// ---- ranks -----------------------------------------------------------------------------------------------------------------
+// rank[i] = #{ j : s[j] > s[i] }: thread i keeps its own score and counts over all scores, tiled through LDS (every lane reads
+// the same LDS word: a broadcast).  The count of one sample does not depend on the grid.  packed[i] = rank << 1 | (label == pos).
+template <typename T>
+__global__ void __launch_bounds__(MT_BLOCK) score_ranks_kernel(const T* __restrict__ s, int64_t stride, int n,
+                                                               const int32_t* __restrict__ labels, int pos_label,
+                                                               int32_t* __restrict__ rank, int32_t* __restrict__ packed,
+                                                               uint32_t* __restrict__ flag) {
+    __shared__ T tile[MT_TILE];
+    const int i = blockIdx.x * MT_BLOCK + threadIdx.x;
+    const T mine = i < n ? s[(int64_t)i * stride] : (T)0;
+    int cnt = 0;
+    for (int t0 = 0; t0 < n; t0 += MT_TILE) {
+        const int len = n - t0 < MT_TILE ? n - t0 : MT_TILE;
+        __syncthreads();
+        for (int j = threadIdx.x; j < len; j += MT_BLOCK) tile[j] = s[(int64_t)(t0 + j) * stride];
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < len; ++j) cnt += tile[j] > mine ? 1 : 0;
+    }
+    if (i >= n) return;
+    unsigned bad = 0;
+    if (!(fabs((double)mine) <= 1.7976931348623157e308)) bad |= 1u;          // NaN / Inf
+    if (rank) rank[i] = cnt;
+    if (labels) {
+        const int32_t l = labels[i];
+        if (l != 0 && l != 1) bad |= 2u;
+        packed[i] = (cnt << 1) | (l == pos_label ? 1 : 0);
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+// ---- shared pieces of the two curve kernels ----------------------------------------------------------------------------------
+// A histogram word holds the bin's positives in its upper and its negatives in its lower 16 bits: at most m <= 16384 draws per
+// resample, so neither half can carry.
+__device__ __forceinline__ int h_tp(uint32_t w) { return (int)(w >> 16); }
+__device__ __forceinline__ int h_fp(uint32_t w) { return (int)(w & 0xffffu); }
+
+// zero the n bins, then add the m draws of this resample (idx row, or the identity when idx is NULL).  An index or a rank
+// outside [0, n) is not followed: it raises flag bit 2.
+__device__ __forceinline__ void fill_hist(uint32_t* hist, const int32_t* __restrict__ packed, int n,
+                                          const int32_t* __restrict__ idx, int m, uint32_t* flag) {
+    for (int g = threadIdx.x; g < n; g += MT_BLOCK) hist[g] = 0u;
+    __syncthreads();
+    for (int k = threadIdx.x; k < m; k += MT_BLOCK) {
+        const int i = idx ? idx[k] : k;
+        if ((unsigned)i >= (unsigned)n) { atomicOr(flag, 4u); continue; }
+        const int32_t w = packed[i];
+        if ((unsigned)(w >> 1) >= (unsigned)n) { atomicOr(flag, 4u); continue; }      // (not a word koaf_score_ranks wrote for this n)
+        atomicAdd(&hist[w >> 1], (w & 1) ? 0x10000u : 1u);
+    }
+    __syncthreads();
+}
+
+// thread t owns bins [t * L, min(n, (t + 1) * L)), L = ceil(n / 256): its (tp, fp) totals, then the exclusive prefix over the
+// threads before it and the block totals -- integer sums, any order gives the same value
+__device__ __forceinline__ void run_prefix(const uint32_t* hist, int n, int* s_tp, int* s_fp, int& g0, int& g1, int& tp_before,
+                                           int& fp_before, int& P, int& N) {
+    const int L = (n + MT_BLOCK - 1) / MT_BLOCK;
+    g0 = threadIdx.x * L < n ? threadIdx.x * L : n;
+    g1 = g0 + L < n ? g0 + L : n;
+    int tp = 0, fp = 0;
+    for (int g = g0; g < g1; ++g) { const uint32_t w = hist[g]; tp += h_tp(w); fp += h_fp(w); }
+    s_tp[threadIdx.x] = tp;
+    s_fp[threadIdx.x] = fp;
+    __syncthreads();
+    tp_before = fp_before = P = N = 0;
+    for (int t = 0; t < MT_BLOCK; ++t) {
+        const int a = s_tp[t], b = s_fp[t];
+        if (t < (int)threadIdx.x) { tp_before += a; fp_before += b; }
+        P += a;
+        N += b;
+    }
+}
+
+// ---- curve metrics of R resamples ------------------------------------------------------------------------------------------
+// Block r: the histogram of resample r, then per thread one ordered walk over the non-empty bins of its run (descending score =
+// ascending rank), then a fixed-order tree over the 256 partial sums.  out[r][0..8): n_pos, n_neg, roc_auc, avg_precision,
+// calibrated avg_precision, 0, 0, 0.
+template <int BINS>
+__global__ void __launch_bounds__(MT_BLOCK) curve_metrics_kernel(const int32_t* __restrict__ packed, int n,
+                                                                 const int32_t* __restrict__ idx, int m, int with_identity,
+                                                                 double pi0, double* __restrict__ out, uint32_t* __restrict__ flag) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t hist[BINS];
+    __shared__ int s_tp[MT_BLOCK], s_fp[MT_BLOCK];
+    __shared__ long long r_auc[MT_BLOCK];
+    __shared__ double r_ap[MT_BLOCK], r_cal[MT_BLOCK];
+    const int r = blockIdx.x;
+    const int32_t* row = nullptr;
+    int draws = n;
+    if (idx != nullptr && !(with_identity && r == 0)) {
+        row = idx + (int64_t)(r - (with_identity ? 1 : 0)) * m;
+        draws = m;
+    }
+    fill_hist(hist, packed, n, row, draws, flag);
+    int g0, g1, tp, fp, P, N;
+    run_prefix(hist, n, s_tp, s_fp, g0, g1, tp, fp, P, N);
+    const double dP = (double)P, dN = (double)N;
+    const double pi = dP / (double)(P + N);
+    const double ratio = pi * (1.0 - pi0) / (pi0 * (1.0 - pi));           // (_metrics_wissam.py:151-152, in its order)
+    long long auc = 0;
+    double ap = 0.0, cal = 0.0;
+    if (P > 0 && N > 0) {
+        for (int g = g0; g < g1; ++g) {
+            const uint32_t w = hist[g];
+            if (w == 0u) continue;
+            const int tg = h_tp(w), fg = h_fp(w);
+            auc += (long long)fg * (long long)(2 * tp + tg);
+            tp += tg;
+            fp += fg;
+            if (tg != 0) {
+                const double dr = (double)tg / dP, dtp = (double)tp;
+                ap += dr * (dtp / (double)(tp + fp));
+                const double den = dtp + ratio * (double)fp;
+                cal += dr * (den == 0.0 ? 0.0 : dtp / den);
+            }
+        }
+    }
+    r_auc[threadIdx.x] = auc;
+    r_ap[threadIdx.x] = ap;
+    r_cal[threadIdx.x] = cal;
+    __syncthreads();
+    for (int o = MT_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            r_auc[threadIdx.x] += r_auc[threadIdx.x + o];
+            r_ap[threadIdx.x] += r_ap[threadIdx.x + o];
+            r_cal[threadIdx.x] += r_cal[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double* o = out + (int64_t)r * 8;
+        const bool ok = P > 0 && N > 0;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        o[0] = dP;
+        o[1] = dN;
+        o[2] = ok ? (double)r_auc[0] / (2.0 * dP * dN) : nan;
+        o[3] = ok ? r_ap[0] : nan;
+        o[4] = ok ? r_cal[0] : nan;
+        o[5] = o[6] = o[7] = 0.0;
+    }
+}
+
+// ---- point estimates ---------------------------------------------------------------------------------------------------------
+// One block, the identity resample.  The Youden cutoff of sensitivity_specificity_cutoff (:224-254): the first maximum of
+// tps / P - fps / N over the points roc_curve(drop_intermediate=True) keeps -- the first threshold, the last one and every one
+// whose (tp, fp) increment differs from the NEXT threshold's (a non-zero second difference of tps or fps) -- behind the leading
+// (0, 0, inf) point, whose value is 0.  Then the confusion counts at `s > thr` and at `s >= cutoff`.
+// out[0] = cutoff (a score value, or +inf), out[1..5) = tn, fp, fn, tp at s > thr, out[5..9) = the same at s >= cutoff.
+template <typename T, int BINS>
+__global__ void __launch_bounds__(MT_BLOCK) point_metrics_kernel(const T* __restrict__ s, int64_t stride,
+                                                                 const int32_t* __restrict__ packed, int n, double thr,
+                                                                 double* __restrict__ out, uint32_t* __restrict__ flag) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t hist[BINS];
+    __shared__ int s_tp[MT_BLOCK], s_fp[MT_BLOCK];
+    __shared__ double r_j[MT_BLOCK];
+    __shared__ int r_g[MT_BLOCK];
+    __shared__ int s_first, s_cnt[8];
+    fill_hist(hist, packed, n, nullptr, n, flag);
+    int g0, g1, tp, fp, P, N;
+    run_prefix(hist, n, s_tp, s_fp, g0, g1, tp, fp, P, N);
+    const double dP = (double)P, dN = (double)N;
+    double best = 0.0;                 // the (0, 0, inf) point
+    int best_g = -1;
+    for (int g = g0; g < g1; ++g) {
+        const uint32_t w = hist[g];
+        if (w == 0u) continue;
+        const bool first = tp + fp == 0;
+        tp += h_tp(w);
+        fp += h_fp(w);
+        bool keep = first || tp + fp == P + N;
+        if (!keep) {
+            int q = g + 1;
+            while (q < n && hist[q] == 0u) ++q;    // the next non-empty bin (one exists: this is not the last)
+            keep = q >= n || hist[q] != w;
+        }
+        if (keep) {
+            const double j = (double)tp / dP - (double)fp / dN;
+            if (j > best) { best = j; best_g = g; }
+        }
+    }
+    r_j[threadIdx.x] = best;
+    r_g[threadIdx.x] = best_g;
+    if (threadIdx.x == 0) s_first = n;
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    // first maximum: the larger value, and of two equal ones the earlier position (the lower bin; -1 is the leading point)
+    for (int o = MT_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o && (r_j[threadIdx.x + o] > r_j[threadIdx.x] ||
+                                     (r_j[threadIdx.x + o] == r_j[threadIdx.x] && r_g[threadIdx.x + o] < r_g[threadIdx.x]))) {
+            r_j[threadIdx.x] = r_j[threadIdx.x + o];
+            r_g[threadIdx.x] = r_g[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    const int cut_g = r_g[0];
+    if (cut_g >= 0) {                   // the score of that rank: the first sample that carries it (all of them are equal)
+        int mine = n;
+        for (int i = threadIdx.x; i < n; i += MT_BLOCK)
+            if ((packed[i] >> 1) == cut_g && i < mine) mine = i;
+        if (mine < n) atomicMin(&s_first, mine);
+    }
+    __syncthreads();
+    const bool inf_cut = cut_g < 0 || s_first >= n;
+    const T cut = inf_cut ? (T)0 : s[(int64_t)s_first * stride];
+    int c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = threadIdx.x; i < n; i += MT_BLOCK) {
+        const T v = s[(int64_t)i * stride];
+        const int pos = packed[i] & 1;
+        c[2 * pos + ((double)v > thr ? 1 : 0)] += 1;
+        c[4 + 2 * pos + ((!inf_cut && v >= cut) ? 1 : 0)] += 1;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (c[k]) atomicAdd(&s_cnt[k], c[k]);
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = inf_cut ? __longlong_as_double(0x7ff0000000000000ll) : (double)cut;
+    if (threadIdx.x < 8) out[1 + threadIdx.x] = (double)s_cnt[threadIdx.x];
+}
+
+}  // namespace
+
+#define STREAM ((hipStream_t)stream)
+
+extern "C" int koaf_score_ranks(const void* scores, int32_t f64, int64_t stride, int32_t n, const int32_t* labels,
+                                int32_t pos_label, int32_t* rank, int32_t* packed, uint32_t* flag, void* stream) {
+    KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N, "koaf_score_ranks: 1 <= n <= %d (n = %d)", MT_MAX_N, n);
+    KOAF_REQUIRE(stride >= 1 && stride < (1ll << 32), "koaf_score_ranks: 1 <= stride < 2^32 (stride = %lld)", (long long)stride);
+    KOAF_REQUIRE(scores && flag && (rank || packed), "koaf_score_ranks: scores, flag and one of rank / packed are required");
+    KOAF_REQUIRE((labels != nullptr) == (packed != nullptr), "koaf_score_ranks: labels and packed go together");
+    const dim3 grid((unsigned)cdiv64(n, MT_BLOCK)), block(MT_BLOCK);
+    if (f64)
+        hipLaunchKernelGGL(score_ranks_kernel<double>, grid, block, 0, STREAM, (const double*)scores, stride, n, labels, pos_label,
+                           rank, packed, flag);
+    else
+        hipLaunchKernelGGL(score_ranks_kernel<float>, grid, block, 0, STREAM, (const float*)scores, stride, n, labels, pos_label,
+                           rank, packed, flag);
+    return koaf_check_launch("koaf_score_ranks");
+}
+
+extern "C" int koaf_curve_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int32_t R, int32_t m,
+                                  int32_t with_identity, double pi0, double* out, uint32_t* flag, void* stream) {
+    KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N, "koaf_curve_metrics: 1 <= n <= %d (n = %d)", MT_MAX_N, n);
+    KOAF_REQUIRE(packed && out && flag, "koaf_curve_metrics: packed, out and flag are required");
+    KOAF_REQUIRE(R >= 0 && R <= (1 << 20), "koaf_curve_metrics: 0 <= R <= 2^20 (R = %d)", R);
+    KOAF_REQUIRE(idx != nullptr || R == 0, "koaf_curve_metrics: R = %d resamples need an index matrix", R);
+    KOAF_REQUIRE(idx == nullptr || (m >= 1 && m <= MT_MAX_N), "koaf_curve_metrics: 1 <= m <= %d (m = %d)", MT_MAX_N, m);
+    KOAF_REQUIRE(pi0 > 0.0 && pi0 < 1.0, "koaf_curve_metrics: 0 < pi0 < 1 (pi0 = %g)", pi0);
+    const int rows = R + (with_identity ? 1 : 0);
+    KOAF_REQUIRE(rows >= 1, "koaf_curve_metrics: nothing to do (R = 0 and no identity row)");
+    const dim3 grid((unsigned)rows), block(MT_BLOCK);
+    const int32_t* ix = R > 0 ? idx : nullptr;
+    if (n <= 4096)
+        hipLaunchKernelGGL(curve_metrics_kernel<4096>, grid, block, 0, STREAM, packed, n, ix, m, with_identity, pi0, out, flag);
+    else
+        hipLaunchKernelGGL(curve_metrics_kernel<MT_MAX_N>, grid, block, 0, STREAM, packed, n, ix, m, with_identity, pi0, out, flag);
+    return koaf_check_launch("koaf_curve_metrics");
+}
+
+extern "C" int koaf_point_metrics(const void* scores, int32_t f64, int64_t stride, const int32_t* packed, int32_t n, double thr,
+                                  double* out, uint32_t* flag, void* stream) {
+    KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N, "koaf_point_metrics: 1 <= n <= %d (n = %d)", MT_MAX_N, n);
+    KOAF_REQUIRE(stride >= 1 && stride < (1ll << 32), "koaf_point_metrics: 1 <= stride < 2^32 (stride = %lld)", (long long)stride);
+    KOAF_REQUIRE(scores && packed && out && flag, "koaf_point_metrics: scores, packed, out and flag are required");
+    const dim3 grid(1), block(MT_BLOCK);
+#define KOAF_PM(T, BINS) hipLaunchKernelGGL((point_metrics_kernel<T, BINS>), grid, block, 0, STREAM, (const T*)scores, stride, packed, n, thr, out, flag)
+    if (f64) { if (n <= 4096) KOAF_PM(double, 4096); else KOAF_PM(double, MT_MAX_N); }
+    else { if (n <= 4096) KOAF_PM(float, 4096); else KOAF_PM(float, MT_MAX_N); }
+#undef KOAF_PM
+    return koaf_check_launch("koaf_point_metrics");
+}

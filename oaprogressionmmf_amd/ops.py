@@ -57,7 +57,7 @@ def _ptr(t):
         return None
     if not t.is_cuda:
         raise KoafError("koaf ops need tensors on a HIP device (no CPU fallback exists)")
-    if t.dtype not in (torch.float32, torch.int64, torch.uint8, torch.float64, torch.bfloat16):   # float64: reduction workspaces only; bfloat16: activation storage mode
+    if t.dtype not in (torch.float32, torch.int64, torch.uint8, torch.float64, torch.bfloat16, torch.int32):   # float64: reduction workspaces, metric scores; bfloat16: activation storage mode; int32: metric ranks / indices
         raise KoafError(f"unexpected dtype {t.dtype}")
     return t.data_ptr()
 
@@ -722,6 +722,118 @@ def attr_fold(acc, g, w, square=False, first=False, x=None, base=None):
     check(lib().koaf_attr_fold(_ptr(acc), _ptr(g), _ptr(w), _ptr(x), _ptr(bt), bv, J, B, n, 1 if square else 0, 1 if first else 0,
                                1 if x is not None else 0, _stream()), "attr_fold")
     return acc
+
+
+# ------------------------------------------------------------------------------------------------
+# validation / evaluation metrics (calc_metrics_v2, calc_bootstrap)
+# ------------------------------------------------------------------------------------------------
+METRICS_MAX_N = defines()["KOAF_METRICS_MAX_N"]
+METRICS_FLAG_TEXT = {1: "Input contains NaN or infinity.", 2: "a label other than 0 / 1 (binary targets only)",
+                     4: "an index of the resampling matrix lies outside [0, n)"}
+
+
+def metrics_flag(device):
+    """a zeroed flag word for the three metric kernels (koaf.h: bit 0 a non-finite score, 1 a non-binary label, 2 a wild index)"""
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def metrics_raise(word):
+    """the ValueError of a flag word read back from the device (sklearn raises one for non-finite scores); 0 passes"""
+    word = int(word) & 7
+    if word:
+        raise ValueError("; ".join(text for bit, text in METRICS_FLAG_TEXT.items() if word & bit))
+
+
+def _metric_scores(what, s):
+    """(n, stride) of a 1-D fp32 / fp64 device vector with a positive stride: a column of an (n, classes) tensor is read in place"""
+    if not torch.is_tensor(s) or s.dtype not in (torch.float32, torch.float64) or s.dim() != 1 or s.numel() == 0 or s.stride(0) < 1:
+        raise KoafError(f"{what}: the scores are a non-empty 1-D fp32 / fp64 device vector with a positive stride, got "
+                        f"{(tuple(s.shape), s.dtype, s.stride()) if torch.is_tensor(s) else type(s)}")
+    return int(s.numel()), int(s.stride(0))
+
+
+def _metric_i32(what, name, t, like, shape=None):
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != like.device \
+            or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise KoafError(f"{what}: {name} is a contiguous int32 tensor{'' if shape is None else ' ' + str(list(shape))} on the scores' "
+                        f"device, got {(tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)}")
+
+
+def score_ranks(scores, labels=None, pos_label=1, flag=None):
+    """rank[i] = #{j : scores[j] > scores[i]} (int32; ties share a rank, the comparison is made in the scores' own dtype) of a
+    1-D fp32 / fp64 device vector of any positive stride, n <= METRICS_MAX_N (koaf_score_ranks: all-pairs counting).  With labels
+    (int32 [n], values 0 / 1) also packed[i] = rank[i] << 1 | (labels[i] == pos_label), what curve_metrics / point_metrics read:
+    -> (rank, packed).  flag: a metrics_flag() word the kernel raises bits of; None: an own word is read back here (a host
+    sync) and a non-finite score or a non-binary label raises ValueError."""
+    n, stride = _metric_scores("score_ranks", scores)
+    if labels is not None:
+        _metric_i32("score_ranks", "labels", labels, scores, (n,))
+    own = flag is None
+    if own:
+        flag = metrics_flag(scores.device)
+    _metric_i32("score_ranks", "flag", flag, scores, (1,))
+    rank = torch.empty(n, dtype=torch.int32, device=scores.device)
+    packed = torch.empty(n, dtype=torch.int32, device=scores.device) if labels is not None else None
+    check(lib().koaf_score_ranks(_ptr(scores), 1 if scores.dtype == torch.float64 else 0, stride, n, _ptr(labels), int(pos_label),
+                                 _ptr(rank), _ptr(packed), _ptr(flag), _stream()), "score_ranks")
+    if own:
+        metrics_raise(flag.item())
+    return rank if labels is None else (rank, packed)
+
+
+def curve_metrics(packed, idx=None, with_identity=True, pi0=0.12, out=None, flag=None):
+    """out [rows, 8] fp64, row r = (n_pos, n_neg, roc_auc, avg_precision, avg_precision calibrated to the prevalence pi0, 0, 0, 0)
+    of one resample of the n samples behind packed (score_ranks): row 0 the sample itself when with_identity, then one row per
+    row of idx (int32 [R, m] device indices into the sample, m <= METRICS_MAX_N; None: no resamples).  One block per row
+    (koaf_curve_metrics: integer histograms, fixed-order fp64 sums -- identical bits from run to run).  A row without positives or
+    without negatives holds its counts and NaN.  flag as in score_ranks (a wild index is skipped and raises)."""
+    if not torch.is_tensor(packed) or not packed.is_cuda:
+        raise KoafError("curve_metrics: packed is the device tensor score_ranks returns")
+    _metric_i32("curve_metrics", "packed", packed, packed)
+    n = int(packed.numel())
+    R = m = 0
+    if idx is not None:
+        _metric_i32("curve_metrics", "idx", idx, packed)
+        if idx.dim() != 2 or idx.numel() == 0:
+            raise KoafError(f"curve_metrics: idx is a non-empty [R, m] matrix, got {tuple(idx.shape)}")
+        R, m = int(idx.shape[0]), int(idx.shape[1])
+    rows = R + (1 if with_identity else 0)
+    if rows == 0:
+        raise KoafError("curve_metrics: neither the identity row nor an index matrix")
+    if out is None:
+        out = torch.empty((rows, 8), dtype=torch.float64, device=packed.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (rows, 8) or out.device != packed.device:
+        raise KoafError(f"curve_metrics: out is contiguous fp64 [{rows}, 8] on packed's device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(packed.device)
+    _metric_i32("curve_metrics", "flag", flag, packed, (1,))
+    check(lib().koaf_curve_metrics(_ptr(packed), n, _ptr(idx), R, m, 1 if with_identity else 0, float(pi0), _ptr(out), _ptr(flag),
+                                   _stream()), "curve_metrics")
+    if own:
+        metrics_raise(flag.item())
+    return out
+
+
+def point_metrics(scores, packed, thr=0.5, out=None, flag=None):
+    """out [9] fp64 of the sample itself: out[0] the Youden cutoff as the reference's sensitivity_specificity_cutoff picks it
+    (first maximum over the points roc_curve(drop_intermediate=True) keeps; a score value, or +inf), out[1:5] = (tn, fp, fn, tp)
+    of `scores > thr`, out[5:9] the same of `scores >= cutoff` (koaf_point_metrics, one block).  scores / packed as in score_ranks."""
+    n, stride = _metric_scores("point_metrics", scores)
+    _metric_i32("point_metrics", "packed", packed, scores, (n,))
+    if out is None:
+        out = torch.empty(9, dtype=torch.float64, device=scores.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (9,) or out.device != scores.device:
+        raise KoafError(f"point_metrics: out is contiguous fp64 [9] on the scores' device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(scores.device)
+    _metric_i32("point_metrics", "flag", flag, scores, (1,))
+    check(lib().koaf_point_metrics(_ptr(scores), 1 if scores.dtype == torch.float64 else 0, stride, _ptr(packed), n, float(thr),
+                                   _ptr(out), _ptr(flag), _stream()), "point_metrics")
+    if own:
+        metrics_raise(flag.item())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""Step bodies of the reference's drivers (koafusion/run/train_prog_fus.py, eval_prog_fus.py) on the MI355X
-path.  The drivers themselves (hydra, data loaders, tensorboard, metrics) stay the reference's."""
-from ._steps import downscale_inputs, train_epoch, train_step, predict_batch
+"""Step bodies and regimes of the reference's drivers (koafusion/run/train_prog_fus.py, eval_prog_fus.py) on the MI355X
+path: train, validation (with its metrics table, various.calc_metrics_v2), evaluation and explanation.  The drivers' shell
+(hydra, data loaders, tensorboard, fit()'s checkpoint bookkeeping) stays the reference's."""
+from ._steps import downscale_inputs, train_epoch, train_step, predict_batch, val_epoch
 from ._eval import eval_epoch, ensemble_eval_foldw, InferenceTimer
 from ._graph import GraphedPredictor, GraphedTrainStep
 from ._accum import GradientFold, micro_batch_weights, train_step_accum
@@ -9,7 +10,7 @@ from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ab
 from ._gradcam import GradCam, cam_strides, gradcam
 from ._attr import attribution_totals, integrated_gradients, quadrature, smoothgrad
 
-__all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "eval_epoch", "ensemble_eval_foldw",
+__all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "val_epoch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
            "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum", "GradCam",
            "cam_strides", "gradcam", "attribution_totals", "integrated_gradients", "quadrature", "smoothgrad"]

@@ -1,5 +1,6 @@
-"""One train iteration / one inference batch (reference: koafusion/run/train_prog_fus.py:100-168,
+"""One train iteration / one inference batch / one validation pass (reference: koafusion/run/train_prog_fus.py:100-236,
 koafusion/run/eval_prog_fus.py:262-303)."""
+import numpy as np
 import torch
 
 from .. import ops, preproc
@@ -76,3 +77,29 @@ def predict_batch(model, xs, downscale=None):
         logits = logits.contiguous()      # (B, head*cls), "b head cls -> b (head cls)" in every model
         proba = softmax_rows_(logits.clone())
     return logits, proba
+
+
+def val_epoch(model, loss_fn, batches, downscale=None, *, target, kws_metrics=None):
+    """`ProgressionPrediction.val_epoch` (train_prog_fus.py:172-236) over an iterable of (xs, ys) device batches; the model must
+    already be in eval() mode.  Per batch one forward (predict_batch) and the loss of its logits, all under no_grad; the
+    probabilities and targets stay on the device and go to various.calc_metrics_v2 as device tensors, the losses are read back
+    once at the end and the numerics status words are looked at once per pass: no per-batch host sync.
+    target: config.data.target (calc_metrics_v2 refuses names it does not know); kws_metrics: further keyword arguments of
+    calc_metrics_v2 (bootstrap, kws_ppv, kws_bs).
+    Returns the reference's dict: {"batch-w": {"loss_prog": [np.round(loss, 3), ...]}, "epoch-w": calc_metrics_v2(...)} --
+    fit() reads its checkpoint criterion from it (the mean of loss_prog, or epoch-w's b_accuracy / avg_precision)."""
+    from ..various._metrics import calc_metrics_v2
+    losses, probas, targets = [], [], []
+    with torch.no_grad():
+        for xs, ys in batches:
+            logits, proba = predict_batch(model, xs, downscale)
+            losses.append(loss_fn(logits.squeeze(1), ys.long().squeeze(1)))
+            probas.append(proba)
+            targets.append(ys.reshape(-1))
+        if not losses:
+            raise ValueError("val_epoch: no batches")
+        loss_host = torch.stack(losses).cpu()
+        epoch_w = calc_metrics_v2(prog_target=torch.cat(targets), prog_pred_proba=torch.cat(probas, dim=0), target=target,
+                                  **(kws_metrics or {}))
+    ops.check_numerics()
+    return {"batch-w": {"loss_prog": [np.round(float(v), 3) for v in loss_host]}, "epoch-w": epoch_w}
