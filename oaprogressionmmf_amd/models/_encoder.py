@@ -17,15 +17,15 @@ MI355X-first layout of the computation (all activations NHWC fp32, rows = (image
   * ResNeXt's grouped 3x3 runs on the same GEMM as 64-channel block-diagonal slabs.
 Parameter gradients are written straight into the flat gradient arena.
 """
+import os
+from collections import namedtuple
+
 import torch
 from torch import nn
 
 from .. import ops
 from ..arena import deliver_grad, grad_target, packed_weight, weight_planes
 from ._core_fes import BasicBlock, Bottleneck
-
-
-import os
 
 USE_SIDE_STREAM = os.environ.get("KOAF_SIDE_STREAM", "1") != "0"
 
@@ -45,16 +45,18 @@ def _stat_shift(bn, train):
 
 # The bottleneck tail y = relu(bn3(c3) + identity) of a block (identity = the block input, or BatchNorm(downsample conv)) is not
 # run as an element-wise pass: the NEXT block's conv1 forms it while it loads its operand and writes y once (ops.conv2d_fwd tail_idt; koaf.h
-# KoafOperand.tf 3) -- 12 B per element of c3 / identity / y traffic instead of 12 + 4.  KOAF_FUSE_TAIL=0 keeps the pass.
-FUSE_TAIL = os.environ.get("KOAF_FUSE_TAIL", "1") != "0"
-FUSE_TAIL_DS = os.environ.get("KOAF_FUSE_TAIL_DS", "1") != "0"      # ... also behind blocks with a downsample branch
+# KoafOperand.tf 3) -- 12 B per element of c3 / identity / y traffic instead of 12 + 4; the identity may itself be the BatchNorm of
+# a downsample branch.  Where the next conv1 cannot take it (_can_take_tail) the element-wise pass ops.bn_add_relu runs.
+# c, saved: the block's last conv output and its BatchNorm record; idt, idsaved: the identity and, behind a downsample branch, its
+# BatchNorm record (else None); out: the buffer y is written to.
+_Tail = namedtuple("_Tail", "c saved idt out idsaved")
 
 
 def _can_take_tail(blk):
     """can this block's first convolution form the previous block's tail on load?  (1x1 / stride 1 on the fp16 scheme with
     its weight plane images current)"""
     c = getattr(blk, "conv1", None)
-    if not (FUSE_TAIL and isinstance(blk, Bottleneck) and c is not None and ops.CONV_F16):
+    if not (isinstance(blk, Bottleneck) and c is not None and ops.CONV_F16):
         return False
     if c.kernel_size != (1, 1) or c.stride != (1, 1) or c.groups != 1 or c.in_channels % 32:
         return False
@@ -62,18 +64,12 @@ def _can_take_tail(blk):
     return img is not None and img[0] is not None
 
 
-KEEP_PLANES_RECOMPUTE = os.environ.get("KOAF_KEEP_PLANES_RECOMPUTE", "1") != "0"
-
-
 # The plane images a 3x3 convolution gathers from are cut by the epilogue of the convolution that PRODUCES its input whenever the
 # BatchNorm between the two is already known -- eval mode, and every stage rebuilt in backward from its saved statistics -- instead
-# of by a pass of their own over the stored tensor (ops.conv2d_fwd emit; koaf.h KoafEmit).  KOAF_EMIT_PLANES=0 keeps the pass.
-EMIT_PLANES = os.environ.get("KOAF_EMIT_PLANES", "1") != "0"
-
-
+# of by a pass of their own over the stored tensor (ops.conv2d_fwd emit; koaf.h KoafEmit).
 def _takes_planes(conv):
     """does this convolution gather its input from activation plane images (ops.conv2d_fwd's own rule)?"""
-    if not (EMIT_PLANES and ops.CONV_F16 and (ops.APLANES_MASK & 1)):
+    if not (ops.CONV_F16 and (ops.APLANES_MASK & 1)):
         return False
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.groups != 1:
         return False
@@ -81,22 +77,21 @@ def _takes_planes(conv):
     return img is not None and img[0] is not None and ops.use_aplanes(img, 3, 3, conv.in_channels)
 
 
-def _conv_fwd(x, conv, N, H, W, in_saved, train, bn=None, tail_idt=None, tail_out=None, tail_idsaved=None, keep_planes=False, emit=None):
-    """bn: the BatchNorm that consumes this conv's output statistics; tail_idt: x / in_saved are the previous block's last
-    conv output and BatchNorm, tail_idt its identity -- the input is their bottleneck tail, formed on load (then the sixth
-    return value is that input, written by the convolution)"""
+def _conv_fwd(x, conv, N, H, W, in_saved, train, bn=None, tail=None, keep_planes=False, emit=None):
+    """-> (y, part, OH, OW, wexp, yin).  bn: the BatchNorm that consumes this conv's output statistics; tail (a _Tail, with
+    x = tail.c and in_saved = tail.saved): the input is the previous block's bottleneck tail, formed on load and written to
+    tail.out -- that is yin, None without a tail"""
     w = packed_weight(conv.weight)
     cin, cout = conv.in_channels, conv.out_channels
     k, s, p, g = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.groups
     sc, sh = (in_saved[2], in_saved[3]) if in_saved is not None else (None, None)
-    wexp = None
+    wexp, yin = None, None
     shift = _stat_shift(bn, train)
-    if tail_idt is not None:
+    if tail is not None:
         y, part, yin = ops.conv2d_fwd(x, w, N, H, W, cin, cout, k, k, s, p, sc, sh, stats=train, shift=shift,
-                                      wimg=weight_planes(conv.weight), tail_idt=tail_idt, tail_out=tail_out,
-                                      tail_idsaved=tail_idsaved, emit=emit)
-        return y, part, ops.conv_out(H, k, s, p), ops.conv_out(W, k, s, p), wexp, yin
-    if g == 1:
+                                      wimg=weight_planes(conv.weight), tail_idt=tail.idt, tail_out=tail.out,
+                                      tail_idsaved=tail.idsaved, emit=emit)
+    elif g == 1:
         y, part = ops.conv2d_fwd(x, w, N, H, W, cin, cout, k, k, s, p, sc, sh, stats=train, shift=shift,
                                  wimg=weight_planes(conv.weight), keep_planes=keep_planes, emit=emit)
     else:
@@ -104,7 +99,7 @@ def _conv_fwd(x, conv, N, H, W, in_saved, train, bn=None, tail_idt=None, tail_ou
             raise NotImplementedError("grouped convolution other than the ResNeXt 3x3 is not built")
         wexp = ops.gconv_expand_w(w, cin, g)
         y, part = ops.gconv3x3_fwd(x, wexp, N, H, W, cin, s, sc, sh, stats=train, shift=shift)
-    return y, part, ops.conv_out(H, k, s, p), ops.conv_out(W, k, s, p), wexp
+    return y, part, ops.conv_out(H, k, s, p), ops.conv_out(W, k, s, p), wexp, yin
 
 
 def _bn_fin(bn, part, count):
@@ -122,22 +117,10 @@ def lane_streams(device, lane):
     """(main, side) HIP streams of encoder lane `lane` on `device` (created once)."""
     key = (device.index, lane)
     if key not in _LANES:
-        # critical path (forward chain, dgrad -> BatchNorm backward) on a HIGH priority stream, the weight
-        # gradients on a LOW priority one: wgrad blocks are dispatched only into what the critical path leaves
-        # free, so they trail behind and fill the HBM-bound BatchNorm phases and GEMM tails
-        hi, lo = _priorities()
-        _LANES[key] = (torch.cuda.Stream(device=device, priority=hi), torch.cuda.Stream(device=device, priority=lo))
+        # main: the critical path (forward chain, dgrad -> BatchNorm backward); side: the weight gradients.  Both at priority 0:
+        # the device has 2 levels only, and the critical path on the higher one measured slower (163 vs 145 ms)
+        _LANES[key] = (torch.cuda.Stream(device=device, priority=0), torch.cuda.Stream(device=device, priority=0))
     return _LANES[key]
-
-
-def _priorities():
-    try:
-        lo, hi = torch.cuda.Stream.priority_range()   # (least, greatest); numerically lower = higher priority
-    except Exception:  # noqa: BLE001
-        lo, hi = 0, -1
-    if os.environ.get("KOAF_STREAM_PRIORITY", "0") == "0":   # measured: 2 levels only; prioritising hurts (163 vs 145 ms)
-        return 0, 0
-    return hi, lo
 
 
 _JOIN = {"queued": False, "streams": []}
@@ -180,7 +163,7 @@ class _SideStream:
         if stream is None:
             key = (device.type, device.index)
             if key not in _SideStream._streams:
-                _SideStream._streams[key] = torch.cuda.Stream(device=device, priority=_priorities()[1])
+                _SideStream._streams[key] = torch.cuda.Stream(device=device, priority=0)
             stream = _SideStream._streams[key]
         self.stream = stream
         self.pending = []
@@ -209,16 +192,14 @@ class _SideStream:
 
 
 # The BatchNorm-backward "apply" (dc = coef0*dz + coef3 - coef2*c) is formed in the loaders of the dgrad / wgrad GEMMs that
-# consume dc (ops.BnApply, koaf.h KoafOperand.tf 2) instead of being written out by an element-wise pass.  KOAF_FUSE_APPLY=0
-# (or convolutions off the fp16 scheme) materialises dc as before.
-FUSE_APPLY = os.environ.get("KOAF_FUSE_APPLY", "1") != "0"
-WGRAD_EARLY = os.environ.get("KOAF_WGRAD_EARLY", "0") == "1"
-
-
+# consume dc (ops.BnApply, koaf.h KoafOperand.tf 2) instead of being written out by an element-wise pass.  Convolutions off the
+# fp16 scheme, grouped ones and weights without plane images get dc as a tensor.
 def _conv_bwd(conv, dc, x, N, H, W, in_saved, wexp, residual=None, need_dx=True, side=None, bnb=None):
-    """weight gradient (x transformed on load by in_saved) and data gradient of one conv.  dc comes out of a BatchNorm
-    backward (_bn_bwd*): either an ops.BnApply -- the recipe of dc, evaluated by the GEMM loaders -- or a tensor carrying
-    max |dc| (dc._koaf_amax); both put the two contractions on the fp16 scheme (koaf.h: KoafGemm.fmt 1)."""
+    """weight gradient (x transformed on load by in_saved) and data gradient of one conv -> (dx, part, dzmax).  dc comes out of
+    a BatchNorm backward (_bn_bwd): either an ops.BnApply -- the recipe of dc, evaluated by the GEMM loaders -- or a tensor carrying
+    max |dc| (dc._koaf_amax); both put the two contractions on the fp16 scheme (koaf.h: KoafGemm.fmt 1).  bnb (_bnb): the
+    data gradient's epilogue reduces the BatchNorm backward of the layer that produced x; part are its partial sums and dzmax
+    the max |dz| it left (None without bnb; dzmax also where bnb did not ask for it)."""
     w = packed_weight(conv.weight)
     cin, cout = conv.in_channels, conv.out_channels
     k, s, p, g = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.groups
@@ -242,25 +223,25 @@ def _conv_bwd(conv, dc, x, N, H, W, in_saved, wexp, residual=None, need_dx=True,
     if side is None and need_dw:
         wgrad()
         deliver_grad(conv.weight, gw, acc)
-    early = side is not None and WGRAD_EARLY and need_dx and g == 1 and k == 1
-    if early:
-        # (A/B switch KOAF_WGRAD_EARLY=1: the 1x1 weight gradient starts TOGETHER with its sibling data gradient -- both stream
-        # through the same (dz, c) tensors, and a second reader close behind the first is served by the 256 MB Infinity Cache)
-        held = dc.tensors() if isinstance(dc, ops.BnApply) else (dc, amax)
-        side.run(held + (x, in_saved), wgrad, conv.weight, gw, acc)
-    dx = None
+    dx = part = dzmax = None
     if need_dx:
-        if g == 1:
-            dx = ops.conv2d_dgrad(dc, w, N, H, W, cin, cout, k, k, s, p, residual=residual, bnb=bnb, wimg=wimg, dy_amax=amax)
-        else:
+        if g != 1:
             assert residual is None and bnb is None
             dx = ops.gconv3x3_dgrad(dc, wexp, N, H, W, cin, s)
-    if side is not None and not early:
+        else:
+            res = ops.conv2d_dgrad(dc, w, N, H, W, cin, cout, k, k, s, p, residual=residual, bnb=bnb, wimg=wimg, dy_amax=amax)
+            if bnb is None:
+                dx = res
+            elif bnb.get("dz_amax"):    # (ops.conv2d_dgrad's return follows its arguments)
+                dx, part, dzmax = res
+            else:
+                dx, part = res
+    if side is not None:
         # enqueued BEHIND the sibling dgrad: the side stream starts this wgrad when the dgrad is done, so it
         # overlaps the HBM-bound BatchNorm backward of the next layer instead of fighting the dgrad for MFMAs
         held = dc.tensors() if isinstance(dc, ops.BnApply) else (dc, amax)
         side.run(held + (x, in_saved), wgrad, conv.weight, gw, acc)
-    return dx
+    return dx, part, dzmax
 
 
 def _bn_train(bn):
@@ -282,58 +263,62 @@ def _bn_deliver(bn, gg, ag, gb, ab):
         deliver_grad(bn.bias, gb, ab)
 
 
-def _bn_bwd(bn, g, c, saved, rows, mask_mode, ymask=None, dz_out=None, dc_out=None, fused=None, pool=None):
-    """-> dc of a BatchNorm(+ReLU mask): an ops.BnApply when the consumers can form it on load (fused), else the tensor"""
+def _bn_bwd(bn, g, c, saved, rows, mask_mode=None, ymask=None, dz_out=None, dc_out=None, pool=None, part=None, dzmax=None):
+    """-> dc of a BatchNorm(+ReLU mask): an ops.BnApply when the consumers can form it on load, else the tensor.
+    part = (partial sums, nsum, i1): the reduction was done by the epilogue of the data gradient that produced g (_bnb), g is
+    the masked dz and dzmax the max |dz| that epilogue left; an un-fused dc is then written to dc_out.  pool: ops.bn_bwd's (the
+    stem: always fused, its consumers are the stem's own kernels)."""
     C = bn.num_features
     (gg, ag), (gb, ab) = _bn_grad_targets(bn)
     train = _bn_train(bn)
-    if fused is None:
-        fused = ops.CONV_F16
-        dc = ops.bn_bwd(g, c, saved, rows, C, rows, gg, gb, mask_mode, ymask=ymask, dz_out=dz_out, fused=fused, train=train)
-        if fused and not FUSE_APPLY:
-            dc = dc.materialize(out=dc_out, want_amax=True)      # (A/B switch: dc written out, with its exact max |dc|)
+    if part is not None:
+        fused = ops.CONV_F16 and dzmax is not None
+        dc = ops.bn_bwd_from_part(*part, g, c, saved, rows, C, rows, gg, gb, dc_out=None if fused else dc_out,
+                                  fused=fused, dzmax=dzmax, train=train)
     else:
         dc = ops.bn_bwd(g, c, saved, rows, C, rows, gg, gb, mask_mode, ymask=ymask, dz_out=dz_out,
-                        dc_out=None if fused else dc_out, fused=fused, pool=pool, train=train)
+                        fused=pool is not None or ops.CONV_F16, pool=pool, train=train)
     _bn_deliver(bn, gg, ag, gb, ab)
     return dc
 
 
-def _bn_bwd_part(bn, part, nsum, i1, dz, c, saved, rows, dc_out=None, dzmax=None):
-    """BatchNorm backward whose reduction was fused into the producing dgrad's epilogue (dzmax: the max |dz| it left)."""
-    C = bn.num_features
-    (gg, ag), (gb, ab) = _bn_grad_targets(bn)
-    fused = ops.CONV_F16 and dzmax is not None
-    dc = ops.bn_bwd_from_part(part, nsum, i1, dz, c, saved, rows, C, rows, gg, gb, dc_out=None if fused else dc_out,
-                              fused=fused, dzmax=dzmax, train=_bn_train(bn))
-    if fused and not FUSE_APPLY:
-        dc = dc.materialize(out=dc_out, want_amax=True)
-    _bn_deliver(bn, gg, ag, gb, ab)
-    return dc
+# BatchNorm-backward reductions ride in the epilogue of the data gradient that produces their input gradient (ops.conv2d_dgrad
+# bnb; koaf.h KoafBnb): mode 2 = a BatchNorm+ReLU between two convolutions, mode 1 = a block's tail (mask from y, a second sum
+# for the BatchNorm of a downsample branch).  What the epilogue left for the tail of the NEXT block of the backward walk:
+_Pend = namedtuple("_Pend", "part nsum dzmax")
 
 
-FUSE_BNB = os.environ.get("KOAF_FUSE_BNB", "1") != "0"
-FUSE_STEM_BWD = os.environ.get("KOAF_FUSE_STEM_BWD", "1") != "0"
-REUSE_STAGE_INPUT = os.environ.get("KOAF_REUSE_STAGE_INPUT", "1") != "0"
+def _bnb(mode, c, saved, y=None, cd=None, sd=None):
+    """epilogue descriptor (ops.conv2d_dgrad bnb) of the BatchNorm over c with record `saved`"""
+    d = dict(mode=mode, c=c, saved=saved, y=y, dz_amax=ops.CONV_F16)
+    if cd is not None:
+        d["c2"], d["saved2"] = cd, sd
+    return d
 
 
 def _tail_bnb(prev):
     """epilogue descriptor for the tail (relu(bn(c_last) + identity)) of block record `prev`"""
-    if prev is None or not FUSE_BNB:
+    if prev is None:
         return None
     c_last, s_last = (prev.c3, prev.s3) if prev.kind == "bottleneck" else (prev.c2, prev.s2)
-    d = dict(mode=1, c=c_last, y=prev.y, saved=s_last, dz_amax=ops.CONV_F16)
-    if prev.cd is not None:
-        d["c2"], d["saved2"] = prev.cd, prev.sd
-    return d
+    return _bnb(1, c_last, s_last, y=prev.y, cd=prev.cd, sd=prev.sd)
+
+
+def _conv_bn_bwd(conv, slot, bn, c, saved, N, H, W, side, wexp=None, epilogue=True):
+    """One step of a block's backward: gradients of `conv` (input relu(bn(c)), c [N,H,W,.] with BatchNorm record `saved`), then
+    the backward of that BatchNorm+ReLU -- reduced in the data gradient's epilogue where `epilogue` -> dc, the gradient w.r.t. c.
+    slot = [the gradient w.r.t. conv's output], emptied here: handed over, not lent, so that it dies when its convolution is
+    done (its plane images, coefficients) and not when this function returns -- the caller keeps no other name for it."""
+    dz, part, dzmax = _conv_bwd(conv, slot.pop(), c, N, H, W, saved, wexp, side=side, bnb=_bnb(2, c, saved) if epilogue else None)
+    return _bn_bwd(bn, dz, c, saved, N * H * W, 2, dc_out=dz, part=None if part is None else (part, 2, 1), dzmax=dzmax)
 
 
 def _block_fwd(blk, y, N, Hc, Wc, train, given, tail=None, defer=False, skip_tail=False):
     """Forward of one residual block.  given = None: statistics are collected by the conv epilogues and
     finalised (normal forward).  given = (s1, s2, s3, sd): activation RECOMPUTE in backward -- the saved
     BatchNorm statistics are reused, nothing is reduced and no running statistic is touched.
-    tail = (c_last, s_last, identity, y buffer, identity's BatchNorm record or None) of the PREVIOUS block whose tail was deferred (y is None then): this block's conv1 forms
-    its own input on load and writes it (r.yin).  defer: leave THIS block's tail to the next block (r.y stays None, r.tail
+    tail: the _Tail of the PREVIOUS block, whose tail was deferred (y is None then): this block's conv1 forms its own input on
+    load and writes it (r.yin).  defer: leave THIS block's tail to the next block (r.y stays None, r.tail
     holds what the next call needs); the caller checks _can_take_tail(next block).  skip_tail: the caller already holds this
     block's output (r.y stays None, nothing is computed for it)."""
     r = _Rec()
@@ -351,48 +336,42 @@ def _block_fwd(blk, y, N, Hc, Wc, train, given, tail=None, defer=False, skip_tai
             s1_pre = fin(blk.bn1, None, N * Hc * Wc, 0)
             emit = (s1_pre[2], s1_pre[3])
         if tail is not None:
-            r.c1, part, _, _, _, y = _conv_fwd(tail[0], blk.conv1, N, Hc, Wc, tail[1], want, blk.bn1, tail_idt=tail[2], tail_out=tail[3],
-                                               tail_idsaved=tail[4], emit=emit)
+            r.c1, part, _, _, _, y = _conv_fwd(tail.c, blk.conv1, N, Hc, Wc, tail.saved, want, blk.bn1, tail=tail, emit=emit)
             r.yin = y
         else:
-            r.c1, part, _, _, _ = _conv_fwd(y, blk.conv1, N, Hc, Wc, None, want, blk.bn1, emit=emit)
+            r.c1, part, _, _, _, _ = _conv_fwd(y, blk.conv1, N, Hc, Wc, None, want, blk.bn1, emit=emit)
         r.s1 = s1_pre if s1_pre is not None else fin(blk.bn1, part, N * Hc * Wc, 0)
         # (rebuilt in backward: the plane images cut for conv2 live on until its weight gradient, a few kernels later, instead of
         # being cut again -- in the forward pass proper they would have to survive the whole step)
-        r.c2, part, OH, OW, r.wexp = _conv_fwd(r.c1, blk.conv2, N, Hc, Wc, r.s1, want, blk.bn2,
-                                               keep_planes=given is not None and KEEP_PLANES_RECOMPUTE)
+        r.c2, part, OH, OW, r.wexp, _ = _conv_fwd(r.c1, blk.conv2, N, Hc, Wc, r.s1, want, blk.bn2, keep_planes=given is not None)
         r.s2 = fin(blk.bn2, part, N * OH * OW, 1)
-        r.c3, part, _, _, _ = _conv_fwd(r.c2, blk.conv3, N, OH, OW, r.s2, want, blk.bn3)
+        r.c3, part, _, _, _, _ = _conv_fwd(r.c2, blk.conv3, N, OH, OW, r.s2, want, blk.bn3)
         r.s3 = fin(blk.bn3, part, N * OH * OW, 2)
         last_c, last_s, cout = r.c3, r.s3, blk.conv3.out_channels
     elif isinstance(blk, BasicBlock):
         r.kind = "basic"
-        r.c1, part, OH, OW, _ = _conv_fwd(y, blk.conv1, N, Hc, Wc, None, want, blk.bn1)
+        r.c1, part, OH, OW, _, _ = _conv_fwd(y, blk.conv1, N, Hc, Wc, None, want, blk.bn1)
         r.s1 = fin(blk.bn1, part, N * OH * OW, 0)
-        r.c2, part, _, _, _ = _conv_fwd(r.c1, blk.conv2, N, OH, OW, r.s1, want, blk.bn2)
+        r.c2, part, _, _, _, _ = _conv_fwd(r.c1, blk.conv2, N, OH, OW, r.s1, want, blk.bn2)
         r.s2 = fin(blk.bn2, part, N * OH * OW, 1)
         last_c, last_s, cout = r.c2, r.s2, blk.conv2.out_channels
     else:
         raise TypeError(f"unsupported block {type(blk)}")
     rows_o = N * OH * OW
+    idt, idsaved = y, None
     if blk.downsample is not None:
-        r.cd, part, _, _, _ = _conv_fwd(y, blk.downsample[0], N, Hc, Wc, None, want, blk.downsample[1])
+        r.cd, part, _, _, _, _ = _conv_fwd(y, blk.downsample[0], N, Hc, Wc, None, want, blk.downsample[1])
         r.sd = fin(blk.downsample[1], part, rows_o, 3)
-        if skip_tail:
-            pass
-        elif defer and FUSE_TAIL_DS:
-            r.tail = (last_c, last_s, r.cd, torch.empty_like(last_c), r.sd)     # (identity = bn_d(cd), formed on load as well)
-        else:
-            r.y = ops.bn_add_relu(last_c, last_s, rows_o, cout, idt=r.cd, idsaved=r.sd)
-    elif skip_tail:
+        idt, idsaved = r.cd, r.sd                 # (identity = bn_d(cd): a deferred tail forms it on load as well)
+    if skip_tail:
         pass
     elif defer:
         # y = relu(bn(last_c) + identity) is formed (and written) by the next block's conv1.  Its buffer is allocated HERE, where
         # the element-wise pass would have allocated its output: the caching allocator then sees the same request order as
         # without the fusion (allocating it at the next conv1 instead cost 17 GB of reserved memory on the headline step)
-        r.tail = (last_c, last_s, y, torch.empty_like(last_c), None)
+        r.tail = _Tail(last_c, last_s, idt, torch.empty_like(last_c), idsaved)
     else:
-        r.y = ops.bn_add_relu(last_c, last_s, rows_o, cout, idt=y)
+        r.y = ops.bn_add_relu(last_c, last_s, rows_o, cout, idt=idt, idsaved=idsaved)
     r.dims = (N, Hc, Wc, OH, OW)
     return r
 
@@ -546,77 +525,43 @@ class EncoderFn(torch.autograd.Function):
     @staticmethod
     def _blocks_bwd(recs, dy, side):
         """backward through a list of block records (last first); returns the gradient w.r.t. the first block's input"""
-        pend = None   # (part, nsum) of THIS block's tail when the previous dgrad's epilogue already reduced it
+        pend = None   # the _Pend of THIS block's tail when the previous dgrad's epilogue already reduced it
         while recs:
             r = recs.pop()
             prev = recs[-1] if recs else None
             blk = r.blk
             N, Hi, Wi, OH, OW = r.dims
-            rows_o, rows_i = N * OH * OW, N * Hi * Wi
+            rows_o = N * OH * OW
             bott = r.kind == "bottleneck"
             tail_bn = blk.bn3 if bott else blk.bn2
             tail_c, tail_s = (r.c3, r.s3) if bott else (r.c2, r.s2)
-            # tail: dz = dy*[y>0] and the BatchNorm behind it
+            # tail: dz = dy*[y>0] and the BatchNorm behind it.  The gradient then travels through the block's convolutions in
+            # `slot`, one step at a time (see _conv_bn_bwd: each step takes it out and the next one is put in)
             if pend is None:
-                dcl = _bn_bwd(tail_bn, dy, tail_c, tail_s, rows_o, 1, ymask=r.y, dz_out=dy)
+                slot = [_bn_bwd(tail_bn, dy, tail_c, tail_s, rows_o, 1, ymask=r.y, dz_out=dy)]
             else:
-                dcl = _bn_bwd_part(tail_bn, pend[0], pend[1], 1, dy, tail_c, tail_s, rows_o, dzmax=pend[2])
+                slot = [_bn_bwd(tail_bn, dy, tail_c, tail_s, rows_o, part=(pend.part, pend.nsum, 1), dzmax=pend.dzmax)]
             dz = dy
-            inner = FUSE_BNB
-            want_max = ops.CONV_F16
-
-            def split(res):
-                """(dz, part, dzmax or None) of a dgrad that carried a fused BatchNorm-backward reduction"""
-                return res if len(res) == 3 else (res[0], res[1], None)
             if bott:
-                g2 = blk.conv2.groups == 1 and inner
-                res = _conv_bwd(blk.conv3, dcl, r.c2, N, OH, OW, r.s2, None, side=side,
-                                bnb=dict(mode=2, c=r.c2, saved=r.s2, dz_amax=want_max) if inner else None)
-                del dcl
-                if inner:
-                    da2, part2, mx2 = split(res)
-                    dc2 = _bn_bwd_part(blk.bn2, part2, 2, 1, da2, r.c2, r.s2, rows_o, dc_out=da2, dzmax=mx2)
-                else:
-                    da2 = res
-                    dc2 = _bn_bwd(blk.bn2, da2, r.c2, r.s2, rows_o, 2, dc_out=da2)
-                res = _conv_bwd(blk.conv2, dc2, r.c1, N, Hi, Wi, r.s1, r.wexp, side=side,
-                                bnb=dict(mode=2, c=r.c1, saved=r.s1, dz_amax=want_max) if g2 else None)
-                del dc2, da2
-                if g2:
-                    da1, part1, mx1 = split(res)
-                    dc1 = _bn_bwd_part(blk.bn1, part1, 2, 1, da1, r.c1, r.s1, rows_i, dc_out=da1, dzmax=mx1)
-                else:
-                    da1 = res
-                    dc1 = _bn_bwd(blk.bn1, da1, r.c1, r.s1, rows_i, 2, dc_out=da1)
+                slot = [_conv_bn_bwd(blk.conv3, slot, blk.bn2, r.c2, r.s2, N, OH, OW, side)]
+                # (a grouped 3x3 has no epilogue: the BatchNorm in front of it reduces in a pass of its own)
+                slot = [_conv_bn_bwd(blk.conv2, slot, blk.bn1, r.c1, r.s1, N, Hi, Wi, side, wexp=r.wexp, epilogue=blk.conv2.groups == 1)]
             else:
-                res = _conv_bwd(blk.conv2, dcl, r.c1, N, OH, OW, r.s1, None, side=side,
-                                bnb=dict(mode=2, c=r.c1, saved=r.s1, dz_amax=want_max) if inner else None)
-                del dcl
-                if inner:
-                    da1, part1, mx1 = split(res)
-                    dc1 = _bn_bwd_part(blk.bn1, part1, 2, 1, da1, r.c1, r.s1, rows_o, dc_out=da1, dzmax=mx1)
-                else:
-                    da1 = res
-                    dc1 = _bn_bwd(blk.bn1, da1, r.c1, r.s1, rows_o, 2, dc_out=da1)
-            first = blk.conv1
+                slot = [_conv_bn_bwd(blk.conv2, slot, blk.bn1, r.c1, r.s1, N, OH, OW, side)]
             # identity branch
             if blk.downsample is not None:
                 if pend is None:
-                    dcd = _bn_bwd(blk.downsample[1], dz, r.cd, r.sd, rows_o, 0, dc_out=dz)
+                    dcd = _bn_bwd(blk.downsample[1], dz, r.cd, r.sd, rows_o, 0)
                 else:
-                    dcd = _bn_bwd_part(blk.downsample[1], pend[0], pend[1], 2, dz, r.cd, r.sd, rows_o, dc_out=dz, dzmax=pend[2])
-                resid = _conv_bwd(blk.downsample[0], dcd, r.yin, N, Hi, Wi, None, None, side=side)
+                    dcd = _bn_bwd(blk.downsample[1], dz, r.cd, r.sd, rows_o, dc_out=dz, part=(pend.part, pend.nsum, 2), dzmax=pend.dzmax)
+                resid = _conv_bwd(blk.downsample[0], dcd, r.yin, N, Hi, Wi, None, None, side=side)[0]
             else:
                 resid = dz
             # block-entry dgrad (+identity gradient); its epilogue reduces the PREVIOUS block's tail BatchNorm(s)
             bnb = _tail_bnb(prev)
-            res = _conv_bwd(first, dc1, r.yin, N, Hi, Wi, None, None, residual=resid, side=side, bnb=bnb)
-            if bnb is not None:
-                dy, part, mx = split(res)
-                pend = (part, 3 if "c2" in bnb else 2, mx)
-            else:
-                dy, pend = res, None
-            del dc1, da1, dz, resid, r
+            dy, part, dzmax = _conv_bwd(blk.conv1, slot.pop(), r.yin, N, Hi, Wi, None, None, residual=resid, side=side, bnb=bnb)
+            pend = _Pend(part, 3 if "c2" in bnb else 2, dzmax) if bnb is not None else None
+            del dz, resid, r
             if side is not None and side.hold:
                 side.join()        # (recompute: the block's tensors may die now, see _SideStream)
         return dy
@@ -643,7 +588,7 @@ class EncoderFn(torch.autograd.Function):
                 sv["recs"] = None
                 if si > 0 and not S["stages"][si - 1]["recompute"]:
                     continue
-                first_in = run[0].yin if REUSE_STAGE_INPUT else None
+                first_in = run[0].yin
                 dy = EncoderFn._blocks_bwd(run, dy, side)
                 run = []
                 next_in = first_in
@@ -652,7 +597,7 @@ class EncoderFn(torch.autograd.Function):
             # outputs are rebuilt (same kernels, saved statistics, no reductions) right before use
             y, Hc2, Wc2 = sv["yin"], sv["H"], sv["W"]
             sv["yin"] = None
-            stage_in, last_y = (y if REUSE_STAGE_INPUT else None), next_in
+            stage_in, last_y = y, next_in
             next_in = None
             if S["block_level"] and len(stages[si]) > 1:
                 # block-granular: pass 1 rebuilds only the block INPUTS of the stage, then every block is rebuilt
@@ -691,13 +636,9 @@ class EncoderFn(torch.autograd.Function):
         w1t = ops.stem_fold_w(packed_weight(conv1.weight)) if (c0 is None or need_dx) else None
         if c0 is None:
             c0 = ops.stem_fwd(S["x"], w1t, N, H, W, dtype=S["adt"])
-        if FUSE_STEM_BWD:
-            # the max-pool's input gradient is gathered inside the BatchNorm reduction and dc0 is formed by the weight gradient
-            # while it loads (dz, c0): neither tensor is written (two of the four passes over the largest activation of the trunk)
-            dc0 = _bn_bwd(bn1, None, c0, S["s0"], N * H1 * W1, 2, fused=True, pool=(dy, S["am"], N, H1, W1))
-        else:
-            da0 = ops.maxpool_bwd(dy, S["am"], N, H1, W1, 64)
-            dc0 = _bn_bwd(bn1, da0, c0, S["s0"], N * H1 * W1, 2, dc_out=da0, fused=False)
+        # the max-pool's input gradient is gathered inside the BatchNorm reduction and dc0 is formed by the weight gradient
+        # while it loads (dz, c0): neither tensor is written (two of the four passes over the largest activation of the trunk)
+        dc0 = _bn_bwd(bn1, None, c0, S["s0"], N * H1 * W1, 2, pool=(dy, S["am"], N, H1, W1))
         if need_dw:
             gw, acc = grad_target(conv1.weight)
             ops.stem_wgrad(dc0, S["x"], gw, N, H, W)
