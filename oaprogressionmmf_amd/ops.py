@@ -498,9 +498,18 @@ def stem_dgrad(dy, w1t, N, H, W):
 # ------------------------------------------------------------------------------------------------
 # batch norm
 # ------------------------------------------------------------------------------------------------
+def _colpart_rows(rows, C, what):
+    """partial rows of the column reductions (koaf_colpart_rows); a width their geometry does not cover (C % 4, C / 4 not a
+    divisor of 256 up to 1024, beyond it not a multiple of 1024) is refused here, before any tensor is sized from it"""
+    n = lib().koaf_colpart_rows(rows, C)
+    if n < 0:
+        raise KoafError(f"{what}: unsupported C={C}")
+    return n
+
+
 def colstats(x, rows, C, shift=None):
     L = lib()
-    part = _empty((L.koaf_colpart_rows(rows, C), 2, C), x)      # (fp32 whatever the storage type of x)
+    part = _empty((_colpart_rows(rows, C, "colstats"), 2, C), x)      # (fp32 whatever the storage type of x)
     r = _i32(0)
     check(L.koaf_colstats(_ptr(x), rows, C, _ptr(part), ctypes.addressof(r), _ptr(shift), _a16(x), _stream()), "colstats")
     return part
@@ -548,7 +557,7 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
         pg, am, pN, pH, pW = pool
         assert g is None and mask_mode == 2 and rows == pN * pH * pW
         dz = dz_out if dz_out is not None else _empty((pN, pH, pW, C), pg)
-        part = _empty((L.koaf_colpart_rows(rows, C), 2, C), pg)
+        part = _empty((_colpart_rows(rows, C, "bn_bwd_reduce_pool"), 2, C), pg)
         r = _i32(0)
         dzmax = _empty((1,), pg) if fused else None
         check(L.koaf_bn_bwd_reduce_pool(_ptr(pg), _ptr(am), _ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(saved[0]), _ptr(saved[1]),
@@ -557,7 +566,7 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
         return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
     if mask_mode != 0 and dz_out is None:
         dz_out = g  # mask in place
-    part = _empty((L.koaf_colpart_rows(rows, C), 2, C), g)
+    part = _empty((_colpart_rows(rows, C, "bn_bwd_reduce"), 2, C), g)
     r = _i32(0)
     dzmax = _empty((1,), g) if fused else None
     check(L.koaf_bn_bwd_reduce(_ptr(g), _ptr(c), _ptr(ymask), _ptr(saved[2]), _ptr(saved[3]), _ptr(saved[0]),
@@ -967,7 +976,10 @@ def layernorm_fwd(x, gamma, beta, rows, D, eps):
 def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, rows, D):
     L = lib()
     dx = torch.empty_like(x)
-    part = _empty((L.koaf_layernorm_bwd_ws(rows, D),), x)
+    n = L.koaf_layernorm_bwd_ws(rows, D)
+    if n < 0:
+        raise KoafError(f"layernorm_bwd: unsupported D={D}")
+    part = _empty((n,), x)
     check(L.koaf_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dgamma),
                                _ptr(dbeta), _ptr(part), rows, D, _stream()), "layernorm_bwd")
     return dx

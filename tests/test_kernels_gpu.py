@@ -1,5 +1,6 @@
 """Kernel-level parity: every libkoaf entry point against a plain torch fp32/fp64 CPU reference of the
-same op (tolerances written at each assert).  All calls go through the C ABI (ctypes).
+same op (tolerances written at each assert).  All calls go through the C ABI (ctypes).  The edge shapes of the element-wise
+kernels -- tails, the grid cap, reduction geometry, pool borders and ties -- are held per element in test_elem_edges_gpu.py.
 
 Contractions: every product -- forward, data- and weight-gradient -- is formed at fp32 rounding level (bars 2e-6 forward,
 BWD = 4e-6 on the longer gradient sums; BASELINE's bar is 1e-3), on either scheme of koaf.h's KoafGemm.fmt: three bf16
