@@ -251,8 +251,8 @@ int koaf_set_conv3x3_halo(int on);
  * with 128-row tiles and K a multiple of 64 run the STREAMED kernel: the four waves of a block each load, transform and split their
  * own 32 rows, two k-tiles ahead in registers, the weight tiles arrive through a three-stage LDS ring, and a persistent block
  * prefetches across tile boundaries.  Same pieces, same MFMA order per accumulator: bit-identical to the block-wide loader.
- * koaf_set_stream(0) sends them through the block-wide loader instead (tests / A-B measurements; environment KOAF_STREAM=0 does the
- * same for a whole process); returns the previous setting.  Process-wide; not meant to be flipped while other threads launch. */
+ * koaf_set_stream(0) sends them through the block-wide loader instead (tests / A-B measurements); on by default; returns the
+ * previous setting.  Process-wide; not meant to be flipped while other threads launch. */
 int koaf_set_stream(int on);
 int64_t koaf_act_planes_elems(int64_t npix, int32_t C);
 int koaf_act_planes(const float* x, const float* x2, int64_t npix, int32_t C, int32_t tf, const float* sc, const float* sh,

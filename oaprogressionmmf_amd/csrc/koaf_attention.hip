@@ -4,6 +4,8 @@
 // with the products formed like every other fp32 contraction here (three bf16 pieces per operand, six MFMAs, KoafGemm.fmt 0).
 // Replaces GEMM -> softmax kernel -> GEMM with two (B, h, n, n) round trips; the attention maps are still emitted (they are
 // returned by the reference, :182).  Block = 4 waves; wave w owns columns [32 w, 32 w + 32) of each 128-wide column chunk.
+// Behind the kernel: the entry points koaf_attention_fwd (the fused kernel, or the three launches for shapes it declines) and
+// koaf_attention_bwd (GEMM chains on koaf_gemm).
 // ================================================================================================
 #include "koaf_gemm_loaders.h"
 
@@ -168,10 +170,92 @@ __global__ void __launch_bounds__(512) attention_fwd_kernel(const float* __restr
 }  // namespace
 
 // returns KOAF_OK when the fused kernel took the call, 1 when the shape is outside it (the caller runs the three-launch path)
-int koaf_attention_fwd_fused(const float* qkv, float* attn, float* out, int32_t B, int32_t n, int32_t h, int32_t d, float scale,
-                             void* stream) {
+static int koaf_attention_fwd_fused(const float* qkv, float* attn, float* out, int32_t B, int32_t n, int32_t h, int32_t d, float scale,
+                                    void* stream) {
     if (n > ATT_NMAX || (d & 3) || !aligned16(qkv) || (int64_t)B * h > 65535) return 1;
     hipLaunchKernelGGL(attention_fwd_kernel, dim3((unsigned)((n + ATT_BM - 1) / ATT_BM), (unsigned)(B * h)), dim3(256, 2), 0,
                        (hipStream_t)stream, qkv, attn, out, n, h, d, scale);
     return koaf_check_launch("koaf_attention_fwd");
+}
+
+// ================================================================================================
+// attention core: S = scale*Q K^T -> softmax -> P V, and its backward (all on koaf_gemm, batched
+// over (b, head) with strided operands straight out of the fused qkv buffer)
+// ================================================================================================
+extern "C" int koaf_attention_fwd(const float* qkv, float* attn, float* out, int32_t B, int32_t n, int32_t h,
+                                  int32_t d, float scale, void* stream) {
+    KOAF_REQUIRE(qkv && attn && out && B > 0 && n > 0 && h > 0 && d > 0, "koaf_attention_fwd: bad args");
+    {
+        const int rc = koaf_attention_fwd_fused(qkv, attn, out, B, n, h, d, scale, stream);
+        if (rc <= 0) return rc;               // taken (or failed); 1 = shape outside the fused kernel: three launches below
+    }
+    const int64_t ld = 3ll * h * d;
+    KoafGemm g;
+    zero_gemm(&g);
+    g.nb0 = B; g.nb1 = h;
+    g.A.ptr = qkv; g.A.kind = 0; g.A.ld = ld; g.A.bs0 = n * ld; g.A.bs1 = d;
+    g.B.ptr = qkv + (int64_t)h * d; g.B.kind = 0; g.B.ld = ld; g.B.bs0 = n * ld; g.B.bs1 = d;
+    g.M = n; g.N = n; g.K = d;
+    g.C = attn; g.ldc = n; g.cbs0 = (int64_t)h * n * n; g.cbs1 = (int64_t)n * n;
+    g.alpha = scale;
+    g.bm = 64; g.bn = 64;
+    int rc = koaf_gemm(&g, stream);
+    if (rc != KOAF_OK) return rc;
+    rc = koaf_softmax_rows(attn, (int64_t)B * h * n, n, stream);
+    if (rc != KOAF_OK) return rc;
+    zero_gemm(&g);
+    g.nb0 = B; g.nb1 = h;
+    g.A.ptr = attn; g.A.kind = 0; g.A.ld = n; g.A.bs0 = (int64_t)h * n * n; g.A.bs1 = (int64_t)n * n;
+    g.B.ptr = qkv + 2ll * h * d; g.B.kind = 1; g.B.ld = ld; g.B.bs0 = n * ld; g.B.bs1 = d;
+    g.M = n; g.N = d; g.K = n;
+    g.C = out; g.ldc = (int64_t)h * d; g.cbs0 = (int64_t)n * h * d; g.cbs1 = d;
+    g.bm = 64; g.bn = 64;
+    return koaf_gemm(&g, stream);
+}
+
+extern "C" int koaf_attention_bwd(const float* dout, const float* qkv, const float* attn, float* dqkv, float* ws,
+                                  int32_t B, int32_t n, int32_t h, int32_t d, float scale, void* stream) {
+    KOAF_REQUIRE(dout && qkv && attn && dqkv && ws && B > 0 && n > 0 && h > 0 && d > 0, "koaf_attention_bwd: bad args");
+    const int64_t ld = 3ll * h * d, hd = (int64_t)h * d;
+    const int64_t pb0 = (int64_t)h * n * n, pb1 = (int64_t)n * n;
+    KoafGemm g;
+    int rc;
+    // dV[j,dd] = sum_i P[i,j] dO[i,dd]
+    zero_gemm(&g);
+    g.prec = 1;
+    g.nb0 = B; g.nb1 = h; g.bm = 64; g.bn = 64;
+    g.A.ptr = attn; g.A.kind = 1; g.A.ld = n; g.A.bs0 = pb0; g.A.bs1 = pb1;
+    g.B.ptr = dout; g.B.kind = 1; g.B.ld = hd; g.B.bs0 = n * hd; g.B.bs1 = d;
+    g.M = n; g.N = d; g.K = n;
+    g.C = dqkv + 2 * hd; g.ldc = ld; g.cbs0 = n * ld; g.cbs1 = d;
+    if ((rc = koaf_gemm(&g, stream)) != KOAF_OK) return rc;
+    // dP[i,j] = sum_dd dO[i,dd] V[j,dd]
+    zero_gemm(&g);
+    g.prec = 1;
+    g.nb0 = B; g.nb1 = h; g.bm = 64; g.bn = 64;
+    g.A.ptr = dout; g.A.kind = 0; g.A.ld = hd; g.A.bs0 = n * hd; g.A.bs1 = d;
+    g.B.ptr = qkv + 2 * hd; g.B.kind = 0; g.B.ld = ld; g.B.bs0 = n * ld; g.B.bs1 = d;
+    g.M = n; g.N = n; g.K = d;
+    g.C = ws; g.ldc = n; g.cbs0 = pb0; g.cbs1 = pb1;
+    if ((rc = koaf_gemm(&g, stream)) != KOAF_OK) return rc;
+    // dS = P * (dP - rowsum(dP*P)) * scale
+    if ((rc = koaf_softmax_bwd_rows(ws, attn, (int64_t)B * h * n, n, scale, stream)) != KOAF_OK) return rc;
+    // dQ[i,dd] = sum_j dS[i,j] K[j,dd]
+    zero_gemm(&g);
+    g.prec = 1;
+    g.nb0 = B; g.nb1 = h; g.bm = 64; g.bn = 64;
+    g.A.ptr = ws; g.A.kind = 0; g.A.ld = n; g.A.bs0 = pb0; g.A.bs1 = pb1;
+    g.B.ptr = qkv + hd; g.B.kind = 1; g.B.ld = ld; g.B.bs0 = n * ld; g.B.bs1 = d;
+    g.M = n; g.N = d; g.K = n;
+    g.C = dqkv; g.ldc = ld; g.cbs0 = n * ld; g.cbs1 = d;
+    if ((rc = koaf_gemm(&g, stream)) != KOAF_OK) return rc;
+    // dK[j,dd] = sum_i dS[i,j] Q[i,dd]
+    zero_gemm(&g);
+    g.prec = 1;
+    g.nb0 = B; g.nb1 = h; g.bm = 64; g.bn = 64;
+    g.A.ptr = ws; g.A.kind = 1; g.A.ld = n; g.A.bs0 = pb0; g.A.bs1 = pb1;
+    g.B.ptr = qkv; g.B.kind = 1; g.B.ld = ld; g.B.bs0 = n * ld; g.B.bs1 = d;
+    g.M = n; g.N = d; g.K = n;
+    g.C = dqkv + hd; g.ldc = ld; g.cbs0 = n * ld; g.cbs1 = d;
+    return koaf_gemm(&g, stream);
 }

@@ -33,6 +33,10 @@ static inline int koaf_check_launch(const char* what) {
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+// a KoafGemm with the defaults every entry point starts from; output size of a convolution along one axis
+static inline void zero_gemm(KoafGemm* g) { *g = KoafGemm{}; g->alpha = 1.f; g->nb0 = g->nb1 = 1; g->splitk = 1; }
+static inline int conv_out(int H, int K, int s, int p) { return (H + 2 * p - K) / s + 1; }
+
 // grid of the grid-stride element-wise kernels (256-thread blocks, `nvec` work items), capped in blocks per CU
 // (KOAF_EW_BLOCKS_PER_CU, default 32) over the chip's 256 CUs: one knob for koaf_elem.hip and koaf_optim.hip
 static inline int ew_blocks_per_cu() {

@@ -115,10 +115,9 @@ void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 lau
 }
 
 namespace {
-int g_stream_mode = -1;     // the streamed A operand for the dense 1x1 kernels: -1 = read KOAF_STREAM once (default on)
+int g_stream_mode = 1;      // koaf_set_stream: the streamed A operand for the dense 1x1 kernels, 1 on (default), 0 off
 // dense K-contiguous fp32 A (1x1 / stride-1 convolutions and their data gradients) in whole k-tiles, an even number of them
 bool stream_ok(const KoafGemm& g) {
-    if (g_stream_mode < 0) { const char* e = getenv("KOAF_STREAM"); g_stream_mode = (e && e[0] == '0') ? 0 : 1; }
     return g_stream_mode == 1 && g.A.kind == 0 && g.A.gather == 0 && g.K >= 2 * BK && (g.K % (2 * BK)) == 0 && g.splitk == 1 &&
            g.nb0 * g.nb1 == 1 && (g.A.tf != 1 || g.K <= STREAM_TAB_K);
 }
@@ -148,7 +147,6 @@ extern "C" int koaf_gemm_pick_tile(const KoafGemm* g, int32_t* bm, int32_t* bn) 
 
 namespace {
 int g_halo_mode = 1;        // koaf_set_conv3x3_halo: 0 off, 1 pick the shape per layer, 2 always 256 rows, 3 always 128 rows
-int g_t2d_mode = -1;        // the 2-D tile kernel (M_PT) for 64- / 128-channel layers whose image tiles evenly: -1 = read KOAF_CONV3_T2D once (default on)
 
 // 3x3 / stride 1 / pad 1 over activation plane images with the whole pixel range as rows: the halo kernel (M_PH)
 bool halo_ok(const KoafGemm& g) {
@@ -175,12 +173,11 @@ TilePlan plan_tiles(const KoafGemm& g) {
     t.vec = gemm_vec_ok(g);
     if (!t.vec) { t.bm = 64; t.bn = 64; }
     t.halo = t.vec && halo_ok(g);
-    if (g_t2d_mode < 0) { const char* e = getenv("KOAF_CONV3_T2D"); g_t2d_mode = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1); }
     // 64 channels in (one halo chunk), 64 / 128 out, images of whole 8 x 16 tiles: the rectangle-tile kernel (halo_ok: 3x3 / stride 1 /
-    // pad 1 over plane images, one GEMM over all pixels, every pixel a row).  KOAF_CONV3_T2D=2 admits 128 input channels as well (two
-    // chunks, the halo fetched twice per 64-column tile: measured no faster than the 128-row raster kernel there, 2.59 vs 2.55 ms).
-    t.t2d = t.halo && g_t2d_mode >= 1 && g_halo_mode == 1 && (g.A.C == 64 || (g.A.C == 128 && g_t2d_mode == 2)) && (g.N == 64 || g.N == 128) &&
-            (g.A.W % 16) == 0 && (g.A.H % 8) == 0 && g.A.zeros != nullptr;
+    // pad 1 over plane images, one GEMM over all pixels, every pixel a row).  (128 input channels -- two chunks, the halo fetched twice
+    // per 64-column tile -- measured no faster than the 128-row raster kernel, 2.59 vs 2.55 ms, and stay with that kernel.)
+    t.t2d = t.halo && g_halo_mode == 1 && g.A.C == 64 && (g.N == 64 || g.N == 128) && (g.A.W % 16) == 0 && (g.A.H % 8) == 0 &&
+            g.A.zeros != nullptr;
     if (t.t2d) {
         t.halo = false;
         t.bm = 128;
@@ -357,7 +354,6 @@ extern "C" int koaf_slab_reduce_epilogue(const float* slabs, int32_t nslab, int3
 }
 
 extern "C" int koaf_set_stream(int on) {
-    if (g_stream_mode < 0) { const char* e = getenv("KOAF_STREAM"); g_stream_mode = (e && e[0] == '0') ? 0 : 1; }
     const int was = g_stream_mode;
     g_stream_mode = on ? 1 : 0;
     return was;

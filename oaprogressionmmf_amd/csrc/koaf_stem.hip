@@ -1,7 +1,7 @@
 // Stem forward on the matrix pipe: the 7x7 / stride-2 / pad-3 convolution of the single-channel image (reference:
 // koafusion/models/_torchvision.py:170, with the 1 -> 3 channel repeat of _xrNmrMcP.py:211-213 folded into the weights) as
 //     y[p][co] = sum_{kh, kw} x[2 oy + kh - 3][2 ox + kw - 3] * w1t[kh * 7 + kw][co],     k = (kh, kw) padded to 8 x 8 = 64.
-// The vector kernel (koaf_conv.hip stem_fwd_kernel) spends 49 multiply-adds per output on the plain FMA pipe and runs at 70 %
+// A vector kernel (retired: DESIGN.md, retired switches) spent 49 multiply-adds per output on the plain FMA pipe and ran at 70 %
 // of that pipe's peak -- twice the time the 12 GB output takes to write.  Here every product is formed like the other fp32
 // contractions of this library (KoafGemm.fmt 0): both operands cut into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 per
 // 16 k (no operand scale: bf16 keeps fp32's exponent range, so raw images of any magnitude are fine).
@@ -11,7 +11,6 @@
 // lane r reads taps 2 r + kw, its left neighbour's pixels shifted by two -- and the weights' fragments stay in registers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cstdlib>
 #include "koaf.h"
 #include "koaf_common.h"
 
@@ -21,6 +20,8 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int SM_TH = 4;                       // output rows per block (one wave each)
+constexpr int SW_TILE_W = 16;                  // output columns per counted tile of the weight gradient: with SM_TH it fixes the slab
+                                               // count, so the order of the sums (stem_wgrad_blocks), not how the kernel walks
 constexpr int SM_BAND = 192;                   // output columns per band (six 32-pixel tiles)
 constexpr int SM_PH = 2 * SM_TH + 5;           // 13 input rows
 constexpr int SM_PW = 2 * SM_BAND + 8;         // 392 input columns (taps 2 ox + 0..7)
@@ -207,24 +208,25 @@ __global__ void __launch_bounds__(256) stem_fwd_mma_kernel(const float* __restri
 }
 }  // namespace
 
-// rows of the statistics buffer (one per block) -- the same tiling as the vector kernel's (koaf_stem_stats_rows)
-int koaf_stem_fwd_mma(const float* x, const float* w1t, float* y, int N, int H, int W, float* stats, const float* stats_shift,
-                      int act16, void* stream) {
-    static const bool off = [] { const char* e = getenv("KOAF_STEM_MMA"); return e && e[0] == '0'; }();
-    if (off) return 1;
-    const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
-    const int64_t units = (int64_t)N * ((OH + SM_TH - 1) / SM_TH);
-    if (units >= (1ll << 31)) return 1;
+#define STREAM ((hipStream_t)stream)
+
+// rows of the statistics buffer: one per unit (image, band of SM_TH output rows)
+extern "C" int32_t koaf_stem_stats_rows(int32_t N, int32_t H) { return (int32_t)((int64_t)N * cdiv64(conv_out(H, 7, 2, 3), SM_TH)); }
+extern "C" int koaf_stem_fwd(const float* x, const float* w1t, float* y, int32_t N, int32_t H, int32_t W,
+                             float* stats, const float* stats_shift, int32_t act16, void* stream) {
+    KOAF_REQUIRE(x && w1t && y && N > 0 && H > 0 && W > 0, "koaf_stem_fwd: bad args");
+    const int OH = conv_out(H, 7, 2, 3), OW = conv_out(W, 7, 2, 3);
+    const int64_t units = (int64_t)N * cdiv64(OH, SM_TH);
+    KOAF_REQUIRE(units < (1ll << 31), "koaf_stem_fwd: grid too large");
     const dim3 grid((unsigned)(units < 512 ? units : 512));          // persistent: two blocks per CU
-    hipStream_t st = (hipStream_t)stream;
     if (stats) {
-        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, true>), grid, dim3(256), 0, st, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
-        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, true>), grid, dim3(256), 0, st, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
+        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, true>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
+        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, true>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
     } else {
-        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, false>), grid, dim3(256), 0, st, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
-        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, false>), grid, dim3(256), 0, st, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
+        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, false>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
+        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, false>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
     }
-    return koaf_check_launch("koaf_stem_fwd/mma");
+    return koaf_check_launch("koaf_stem_fwd");
 }
 
 // ================================================================================================
@@ -234,7 +236,7 @@ int koaf_stem_fwd_mma(const float* x, const float* w1t, float* y, int N, int H, 
 //     in LDS split by column parity (column c = 2 ox + kw: parity kw & 1, half-index ox + (kw >> 1)), each parity twice, the
 //     second copy shifted by one element, so that the eight values are four ds_read_b32 from a 4-byte aligned address whatever
 //     the tap;
-//   * B (pixels x channels): dc itself, formed on load from (dz, c, coef) like the vector kernel (KoafBnApply) or read as given,
+//   * B (pixels x channels): dc itself, formed on load from (dz, c, coef) (KoafBnApply: coef0*dz + coef3 - coef2*c) or read as given,
 //     cut into three bf16 pieces and written by each wave to its own [16 pixels][64 channels] image, read back transposed
 //     (ds_read_b64_tr_b16) -- no block barrier inside a unit;
 //   * every wave (one output row of the unit) accumulates the whole 64 x 64 gradient; the four are summed through LDS at the
@@ -457,20 +459,31 @@ __global__ void __launch_bounds__(256) stem_wgrad_mma_kernel(const float* __rest
 }
 }  // namespace
 
-// 1 = not taken (KOAF_STEM_MMA=0): the vector kernel of koaf_conv.hip; nb = the slab count both kernels use
-int koaf_stem_wgrad_mma(const float* dy, const float* x, float* slabs, int nb, int N, int H, int W, const float* c,
-                        const float* coef, int act16, void* stream) {
-    static const bool off = [] { const char* e = getenv("KOAF_STEM_MMA"); return e && e[0] == '0'; }();
-    if (off) return 1;
-    const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)nb);
-    if (c) {
-        if (act16) hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, true>), grid, dim3(256), 0, st, dy, x, slabs, N, H, W, OH, OW, c, coef);
-        else hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, false>), grid, dim3(256), 0, st, dy, x, slabs, N, H, W, OH, OW, c, coef);
+// slabs of the weight gradient = blocks of its kernel: one per SM_TH x SW_TILE_W tile of the output, 1024 at the most
+static inline int stem_wgrad_blocks(int N, int H, int W) {
+    const int OH = conv_out(H, 7, 2, 3), OW = conv_out(W, 7, 2, 3);
+    int64_t tiles = (int64_t)N * cdiv64(OH, SM_TH) * cdiv64(OW, SW_TILE_W);
+    return (int)(tiles < 1024 ? tiles : 1024);
+}
+extern "C" int64_t koaf_stem_wgrad_ws(int32_t N, int32_t H, int32_t W) {
+    return (int64_t)(stem_wgrad_blocks(N, H, W) + 16) * 49 * 64;
+}
+extern "C" int koaf_stem_wgrad(const float* dy, const float* x, float* dw1t, int32_t N, int32_t H, int32_t W,
+                               float* slabs, const KoafBnApply* dy_apply, int32_t act16, void* stream) {
+    KOAF_REQUIRE((dy || dy_apply) && x && dw1t && slabs && N > 0, "koaf_stem_wgrad: bad args");
+    KOAF_REQUIRE(!dy_apply || (dy_apply->dz && dy_apply->c && dy_apply->coef), "koaf_stem_wgrad: dy_apply needs dz / c / coef");
+    const int OH = conv_out(H, 7, 2, 3), OW = conv_out(W, 7, 2, 3);
+    const int nb = stem_wgrad_blocks(N, H, W);
+    if (dy_apply) {
+        if (act16) hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, true>), dim3(nb), dim3(256), 0, STREAM, dy_apply->dz, x, slabs, N, H, W, OH, OW,
+                                      dy_apply->c, dy_apply->coef);
+        else hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, false>), dim3(nb), dim3(256), 0, STREAM, dy_apply->dz, x, slabs, N, H, W, OH, OW,
+                                dy_apply->c, dy_apply->coef);
     } else
-        hipLaunchKernelGGL((stem_wgrad_mma_kernel<false, false>), grid, dim3(256), 0, st, dy, x, slabs, N, H, W, OH, OW, nullptr, nullptr);
-    return koaf_check_launch("koaf_stem_wgrad/mma");
+        hipLaunchKernelGGL((stem_wgrad_mma_kernel<false, false>), dim3(nb), dim3(256), 0, STREAM, dy, x, slabs, N, H, W, OH, OW, nullptr, nullptr);
+    const int rc = koaf_check_launch("koaf_stem_wgrad");
+    if (rc != KOAF_OK) return rc;
+    return koaf_slab_reduce(slabs, nb, 49 * 64, dw1t, stream);
 }
 
 // ================================================================================================
@@ -571,7 +584,7 @@ extern "C" int koaf_stem_dgrad(const float* dy, const float* w1t, float* dx, int
                                const KoafBnApply* dy_apply, int32_t act16, void* stream) {
     KOAF_REQUIRE((dy || dy_apply) && w1t && dx && N > 0 && H > 0 && W > 0, "koaf_stem_dgrad: bad args");
     KOAF_REQUIRE(!dy_apply || (dy_apply->dz && dy_apply->c && dy_apply->coef), "koaf_stem_dgrad: dy_apply needs dz / c / coef");
-    const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
+    const int OH = conv_out(H, 7, 2, 3), OW = conv_out(W, 7, 2, 3);
     const int tyn = (OH + SD_I - 1) / SD_I, txn = (OW + SD_I - 1) / SD_I;
     const int64_t blocks = (int64_t)N * tyn * txn;
     KOAF_REQUIRE(blocks < (1ll << 31), "koaf_stem_dgrad: grid too large");
@@ -585,4 +598,38 @@ extern "C" int koaf_stem_dgrad(const float* dy, const float* w1t, float* dx, int
     } else
         hipLaunchKernelGGL((stem_dgrad_kernel<false, false>), grid, dim3(256), 0, st, dy, w1t, dx, H, W, OH, OW, tyn, txn, nullptr, nullptr);
     return koaf_check_launch("koaf_stem_dgrad");
+}
+
+// ================================================================================================
+// The 3 repeated input channels folded into the weights, and the gradient spread back over them
+// ================================================================================================
+namespace {
+// w [64][49][3] -> w1t [49][64] (sum over the 3 identical input channels)
+__global__ void stem_fold_kernel(const float* __restrict__ w, float* __restrict__ w1t) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 64 * 49) return;
+    const int co = i / 49, k = i - co * 49;
+    const float* s = w + (int64_t)i * 3;
+    w1t[k * 64 + co] = s[0] + s[1] + s[2];
+}
+__global__ void stem_unfold_kernel(const float* __restrict__ dw1t, float* __restrict__ dw) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 64 * 49) return;
+    const int co = i / 49, k = i - co * 49;
+    const float v = dw1t[k * 64 + co];
+    dw[(int64_t)i * 3 + 0] = v;
+    dw[(int64_t)i * 3 + 1] = v;
+    dw[(int64_t)i * 3 + 2] = v;
+}
+}  // namespace
+
+extern "C" int koaf_stem_fold_w(const float* w, float* w1t, void* stream) {
+    KOAF_REQUIRE(w && w1t, "koaf_stem_fold_w: bad args");
+    hipLaunchKernelGGL(stem_fold_kernel, dim3((64 * 49 + 255) / 256), dim3(256), 0, STREAM, w, w1t);
+    return koaf_check_launch("koaf_stem_fold_w");
+}
+extern "C" int koaf_stem_unfold_dw(const float* dw1t, float* dw, void* stream) {
+    KOAF_REQUIRE(dw1t && dw, "koaf_stem_unfold_dw: bad args");
+    hipLaunchKernelGGL(stem_unfold_kernel, dim3((64 * 49 + 255) / 256), dim3(256), 0, STREAM, dw1t, dw);
+    return koaf_check_launch("koaf_stem_unfold_dw");
 }

@@ -11,7 +11,6 @@
 // Products as everywhere on the fp16 scheme (KoafGemm.fmt 1): operands are two fp16 pieces of value x scale, three MFMAs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <cstdlib>
 #include "koaf.h"
 #include "koaf_pieces.h"
 
@@ -208,7 +207,7 @@ void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 lau
 // stream beside the critical path: blocks of ~0.5 ms give the CUs back often enough; 256 long blocks cost 15 ms per step), whole
 // multiples of 8 (an XCD each)
 static int wg3_nk(int64_t nchunk, int Cin, int Cout) {
-    static const int target = [] { const char* e = getenv("KOAF_WGRAD3_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
+    constexpr int target = 1024;
     const int ncomb = (Cout / 64) * (Cin / 64);
     int64_t nk = target / ncomb;
     if (nk < 8) nk = 8;
@@ -219,8 +218,6 @@ static int wg3_nk(int64_t nchunk, int Cin, int Cout) {
 
 // can the ring kernel take this 3x3 weight gradient?  (geometry only; the caller checks that plane images are given)
 bool koaf_wgrad3_ring_ok(int N, int H, int W, int Cin, int Cout) {
-    static const bool off = [] { const char* e = getenv("KOAF_WGRAD3_RING"); return e && e[0] == '0'; }();
-    if (off) return false;
     const int Wp = W + 2, Hp = H + 2;
     const int D = (Wp + 1 + 31) >> 5;
     return Cin % 64 == 0 && Cout % 64 == 0 && W >= 16 &&      // (narrower images: the zero border is > 25 % of the positions)

@@ -69,7 +69,7 @@ def _can_take_tail(blk):
 # of by a pass of their own over the stored tensor (ops.conv2d_fwd emit; koaf.h KoafEmit).
 def _takes_planes(conv):
     """does this convolution gather its input from activation plane images (ops.conv2d_fwd's own rule)?"""
-    if not (ops.CONV_F16 and (ops.APLANES_MASK & 1)):
+    if not ops.CONV_F16:
         return False
     if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.groups != 1:
         return False

@@ -18,15 +18,10 @@ _i32 = ctypes.c_int32
 # on the bf16 x 3 scheme for A/B runs.
 import os
 CONV_F16 = os.environ.get("KOAF_CONV_FMT", "f16") != "bf16"
-# activation plane images for the gathered (3x3) convolution kernels (koaf_act_planes); KOAF_APLANES=0: fp32 loaders
-APLANES_MASK = int(os.environ.get("KOAF_APLANES", "7"))     # bit 0 forward, 1 data gradient, 2 weight gradient
-APLANES = APLANES_MASK != 0
+# The gathered (3x3) convolution kernels read activation plane images (koaf_act_planes) wherever use_aplanes says they pay; the
+# aplanes= arguments below override that per call (False: the fp32 loaders).  A convolution's forward images are kept for its
+# weight gradient only where the caller asks (keep_planes=): keeping them everywhere fragments the caching allocator's pool.
 ACT_SCALE = defines()["KOAF_ACT_SCALE"]      # the fixed activation scale of the fp16 scheme (koaf.h)
-# Forward plane images of up to this many 16-bit elements are kept on the convolution's output for its weight gradient
-# (saves re-cutting them).  Off by default: the mixed lifetimes fragment the caching allocator's pool -- the headline
-# step's reserved memory went from 240 to 265 GB (of 288) for 1 % of its time with everything kept, and still to 264 GB
-# with only the deep layers' small images.
-KEEP_XPLANES_ELEMS = int(os.environ.get("KOAF_KEEP_XPLANES_ELEMS", "0"))
 
 # Optional live profiler (bench.py): when a list is installed here every MFMA-GEMM based call is bracketed
 # by two events recorded on the stream the kernel is launched on (torch's current stream) and logged as
@@ -221,7 +216,7 @@ def launch_log_read():
 
 def use_aplanes(wimg, KH, KW, C):
     """activation plane images pay where a kernel gathers (every element is otherwise converted KH*KW times)"""
-    return APLANES and wimg is not None and KH * KW > 1 and C % 32 == 0
+    return wimg is not None and KH * KW > 1 and C % 32 == 0
 
 
 def conv2d_fwd(x, w, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None, in_sh=None, stats=False, shift=None, wimg=None,
@@ -251,7 +246,7 @@ def conv2d_fwd(x, w, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None, in_sh=
         part = _empty((nrows, 2, Cout), x)
     e0 = _prof_begin()
     if aplanes is None:
-        aplanes = (APLANES_MASK & 1) and use_aplanes(wimg, KH, KW, Cin) and wimg[0] is not None and stride == 1     # (stride 2: the pre-pass
+        aplanes = use_aplanes(wimg, KH, KW, Cin) and wimg[0] is not None and stride == 1     # (stride 2: the pre-pass
         #                                           would cut four times the pixels the kernel reads)
     xpl = None
     tail = None
@@ -280,7 +275,7 @@ def conv2d_fwd(x, w, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None, in_sh=
                             _img(wimg), xpl.data_ptr() if xpl is not None else None, tail, em, _a16(x), _stream()), "conv2d_fwd")
     if epl is not None:
         y._koaf_eplanes = (epl, emit[0], emit[1])
-    if xpl is not None and not torch.is_tensor(aplanes) and (keep_planes or xpl.numel() <= KEEP_XPLANES_ELEMS):
+    if xpl is not None and not torch.is_tensor(aplanes) and keep_planes:
         y._koaf_xplanes = xpl       # ride on the output: this conv's weight gradient reads them instead of cutting them again
     _prof_end(e0, "gemm", 2.0 * N * OH * OW * Cout * KH * KW * Cin,
               f"conv_fwd k{KH}s{stride} {Cin}->{Cout} px{N*OH*OW}" + (" +tail" if tail is not None else ""),
@@ -307,7 +302,7 @@ def conv2d_dgrad(dy, w, N, H, W, Cin, Cout, KH, KW, stride, pad, residual=None, 
     a16 = _a16(dy.c) if isinstance(dy, BnApply) else (_a16(bnb["c"]) if bnb is not None else 0)
     dx = _empty((N, H, W, Cin), like)
     if aplanes is None:
-        aplanes = ((APLANES_MASK & 2) and use_aplanes(wimg, KH, KW, Cout) and wimg[1] is not None and stride in (1, 2) and
+        aplanes = (use_aplanes(wimg, KH, KW, Cout) and wimg[1] is not None and stride in (1, 2) and
                    (app is not None or dy_amax is not None))
     e0 = _prof_begin()
     dypl = None
@@ -374,7 +369,7 @@ def conv2d_wgrad(dy, x, dw, N, H, W, Cin, Cout, KH, KW, stride, pad, in_sc=None,
     dyp, amp, app, like = _dy_args(dy, dy_amax)
     slabs = _slab_ws(slabs, L.koaf_conv2d_wgrad_ws(N, H, W, Cin, Cout, KH, KW, stride, pad), like, "conv2d_wgrad")
     if aplanes is None:
-        aplanes = ((APLANES_MASK & 4) and KH * KW > 1 and stride == 1 and Cin % 8 == 0 and Cout % 8 == 0 and
+        aplanes = (KH * KW > 1 and stride == 1 and Cin % 8 == 0 and Cout % 8 == 0 and
                    (app is not None or dy_amax is not None))
     e0 = _prof_begin()
     dypl = xpl = None

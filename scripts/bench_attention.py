@@ -1,6 +1,5 @@
-"""Forward attention of the FeaT fusion at the headline shape, one launch (n <= 512) vs the three-launch path
-(KOAF_ATTN_FUSED=0 python scripts/bench_attention.py for the latter; the switch is read once per process)."""
-import os
+"""Forward attention of the FeaT fusion at the headline shapes: the one-launch kernel (n <= 512; longer sequences take the
+three-launch path, whose measured times at these shapes are in DESIGN.md, retired switches)."""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -17,4 +16,4 @@ for (B, n, h, d) in [(8, 483, 8, 256), (8, 161, 8, 256), (8, 92, 8, 256), (8, 25
     e1.record(); torch.cuda.synchronize()
     t = e0.elapsed_time(e1) / 20
     fl = 4.0 * B * h * n * n * d
-    print(f"fused={os.environ.get('KOAF_ATTN_FUSED', '1')} B={B} n={n} h={h} d={d}: {t * 1e3:8.1f} us  {fl / t / 1e9:6.1f} TF/s", flush=True)
+    print(f"B={B} n={n} h={h} d={d}: {t * 1e3:8.1f} us  {fl / t / 1e9:6.1f} TF/s", flush=True)

@@ -97,3 +97,16 @@ def test_slabs_keyword_is_optional():
     from oaprogressionmmf_amd import ops
     for f in (ops.conv2d_wgrad, ops.gconv3x3_wgrad):
         assert inspect.signature(f).parameters["slabs"].default is None
+
+
+@pytest.mark.parametrize("N,H,W", [(1, 9, 9), (1, 8, 70), (3, 33, 50), (2, 384, 384), (1280, 384, 384)])
+def test_stem_slab_count_and_statistics_rows(N, H, W):
+    """The stem's weight gradient sums min(1024, N * ceil(OH / 4) * ceil(OW / 16)) slabs and its forward writes N * ceil(OH / 4)
+    statistics rows: both counts decide the order of fp32 sums, so they are part of what the library computes (koaf_stem.hip:
+    SM_TH, SW_TILE_W).  Read back through koaf_stem_wgrad_ws = (slabs + 16) * 49 * 64 and koaf_stem_stats_rows."""
+    from oaprogressionmmf_amd import _lib
+    L = _lib.lib()
+    OH, OW = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    bands, tiles_w = -(-OH // 4), -(-OW // 16)
+    assert L.koaf_stem_stats_rows(N, H) == N * bands
+    assert L.koaf_stem_wgrad_ws(N, H, W) == (min(1024, N * bands * tiles_w) + 16) * 49 * 64
