@@ -162,8 +162,6 @@ __global__ void __launch_bounds__(AT_BLOCK) attr_fold_kernel(float* __restrict__
 
 }  // namespace
 
-#define STREAM ((hipStream_t)stream)
-
 extern "C" int koaf_path_points(const float* x, const float* base, float base_value, const float* alpha, float* out, int32_t J,
                                 int32_t B, int64_t n, const float* mm, float noise_level, uint64_t seed, int64_t draw0,
                                 void* stream) {

@@ -1,6 +1,6 @@
 // koaf_bce.hip -- binary cross-entropy on probabilities (nn.BCELoss) and on logits (nn.BCEWithLogitsLoss), the registry's
 // "bce_loss" / "bce_wlogits_loss" (koafusion/various/_losses.py:111-117): loss and input gradient in one launch, like the focal
-// kernel (koaf_elem.hip), and with its reduction design -- one block up to its single-block reach, beyond that a grid of
+// kernel (koaf_loss.hip), and with its reduction design -- one block up to its single-block reach, beyond that a grid of
 // fixed-size chunks whose partial sums one block adds in index order.
 #include "koaf_common.h"
 
@@ -87,8 +87,6 @@ __global__ void __launch_bounds__(256) bce_sum_kernel(const float* __restrict__ 
 }
 
 }  // namespace
-
-#define STREAM ((hipStream_t)stream)
 
 extern "C" int64_t koaf_bce_ws(int64_t n) { return n > BCE_ONE_BLOCK ? (n + BCE_CHUNK - 1) / BCE_CHUNK : 0; }
 

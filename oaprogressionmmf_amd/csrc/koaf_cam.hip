@@ -187,16 +187,13 @@ __global__ void __launch_bounds__(256) cam_upsample_slices_kernel(const float* _
 
 }  // namespace
 
-#define STREAM ((hipStream_t)stream)
-
 extern "C" int koaf_cam(const float* A, const float* w, float* cam, float* img_sum, float* img_max, int32_t N, int32_t HW,
                         int32_t C, int32_t relu, int32_t act16, void* stream) {
     KOAF_REQUIRE(A && w && cam && img_sum && img_max && N > 0 && HW > 0 && C > 0, "koaf_cam: bad args");
     KOAF_REQUIRE(C % 4 == 0 && C <= CAM_MAX_C, "koaf_cam: C %% 4 == 0 and C <= %d (C = %d)", CAM_MAX_C, C);
     KOAF_REQUIRE(aligned16(w) && (act16 ? (((uintptr_t)A) & 7) == 0 : aligned16(A)), "koaf_cam: unaligned");
     const size_t lds = (size_t)C * sizeof(float);
-    if (act16) hipLaunchKernelGGL(cam_kernel<true>, dim3(N), dim3(CAM_BLOCK), lds, STREAM, A, w, cam, img_sum, img_max, HW, C, relu);
-    else hipLaunchKernelGGL(cam_kernel<false>, dim3(N), dim3(CAM_BLOCK), lds, STREAM, A, w, cam, img_sum, img_max, HW, C, relu);
+    KOAF_LAUNCH_ACT16(act16, cam_kernel<A16>, dim3(N), dim3(CAM_BLOCK), lds, STREAM, A, w, cam, img_sum, img_max, HW, C, relu);
     return koaf_check_launch("koaf_cam");
 }
 

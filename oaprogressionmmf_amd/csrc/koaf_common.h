@@ -30,6 +30,9 @@ static inline int koaf_check_launch(const char* what) {
     return KOAF_OK;
 }
 
+// the `void* stream` argument of every entry point
+#define STREAM ((hipStream_t)stream)
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
@@ -38,7 +41,8 @@ static inline void zero_gemm(KoafGemm* g) { *g = KoafGemm{}; g->alpha = 1.f; g->
 static inline int conv_out(int H, int K, int s, int p) { return (H + 2 * p - K) / s + 1; }
 
 // grid of the grid-stride element-wise kernels (256-thread blocks, `nvec` work items), capped in blocks per CU
-// (KOAF_EW_BLOCKS_PER_CU, default 32) over the chip's 256 CUs: one knob for koaf_elem.hip and koaf_optim.hip
+// (KOAF_EW_BLOCKS_PER_CU, default 32) over the chip's 256 CUs: one knob for every unit that launches them
+constexpr int EB = 256;  // elementwise block
 static inline int ew_blocks_per_cu() {
     static const int v = [] { const char* e = getenv("KOAF_EW_BLOCKS_PER_CU"); int n = e ? atoi(e) : 32; return n < 1 ? 1 : n; }();
     return v;
@@ -93,7 +97,7 @@ __device__ __forceinline__ void block_amax_raise_bits(unsigned bits, float* slot
 }
 __device__ __forceinline__ void block_amax_raise(float v, float* slot) { block_amax_raise_bits(koaf_absbits(v), slot); }
 
-// The hash of the counter-based generators (dropout masks: koaf_elem.hip; Gaussian draws: koaf_attr.hip): the splitmix64 step.
+// The hash of the counter-based generators (dropout masks: koaf_rows.hip; Gaussian draws: koaf_attr.hip): the splitmix64 step.
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -155,3 +159,11 @@ __device__ __forceinline__ void store4(float* p, int64_t off, v4f v) {
     if constexpr (!H) *(v4f*)(p + off) = v;
     else *(uint2*)(reinterpret_cast<unsigned short*>(p) + off) = round_bf16x4(v);
 }
+
+// hipLaunchKernelGGL of a kernel templated on the activations' storage (bool, true = bf16): the kernel is written with A16 in that
+// place -- k<A16>, or (k<A16, true>) in parentheses where it has further parameters -- and launched with A16 = (act16 != 0)
+#define KOAF_LAUNCH_ACT16(act16, kernel, ...)                                                        \
+    do {                                                                                             \
+        if (act16) { constexpr bool A16 = true; hipLaunchKernelGGL(kernel, __VA_ARGS__); }           \
+        else { constexpr bool A16 = false; hipLaunchKernelGGL(kernel, __VA_ARGS__); }                \
+    } while (0)

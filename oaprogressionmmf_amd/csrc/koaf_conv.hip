@@ -113,8 +113,6 @@ __global__ void __launch_bounds__(256) gconv_compress_kernel(const float* __rest
 
 }  // namespace
 
-#define STREAM ((hipStream_t)stream)
-
 // ================================================================================================
 // dense convolution
 // ================================================================================================

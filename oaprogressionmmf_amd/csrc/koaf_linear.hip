@@ -1,8 +1,6 @@
 // koaf_linear.hip -- nn.Linear on koaf_gemm (split-K for the few-row layers), and the direct kernels of the narrow heads.
 #include "koaf_common.h"
 
-#define STREAM ((hipStream_t)stream)
-
 // split-K plan for a linear layer with few rows: the 64x64-tile grid of M x N is only a few hundred blocks with
 // K/32 serial k-steps each (latency-bound at ~1 block per CU); splitting K 2-8 ways fills the chip.
 struct LinTile { int bm, bn; };

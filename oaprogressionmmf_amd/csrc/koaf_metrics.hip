@@ -235,8 +235,6 @@ __global__ void __launch_bounds__(MT_BLOCK) point_metrics_kernel(const T* __rest
 
 }  // namespace
 
-#define STREAM ((hipStream_t)stream)
-
 extern "C" int koaf_score_ranks(const void* scores, int32_t f64, int64_t stride, int32_t n, const int32_t* labels,
                                 int32_t pos_label, int32_t* rank, int32_t* packed, uint32_t* flag, void* stream) {
     KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N, "koaf_score_ranks: 1 <= n <= %d (n = %d)", MT_MAX_N, n);

@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr int EB = 256;  // elementwise block
-
 // ++step; hyper = {lr, first}: first = 1 on the very first update (SGD starts its momentum buffer with the gradient there), from
 // the device scalars, so that a captured (HIP-graph) optimizer step advances from replay to replay like koaf_adam_hyper's
 __global__ void optim_hyper_kernel(int32_t* step, const float* lr, float* hyper) {
@@ -361,8 +359,6 @@ inline int64_t gn_blocks(int64_t n) { return cdiv64(n, GN_CHUNK); }
 // ================================================================================================
 // C ABI
 // ================================================================================================
-#define STREAM ((hipStream_t)stream)
-
 extern "C" int koaf_optim_hyper(int32_t* step, const float* lr, float* hyper, void* stream) {
     KOAF_REQUIRE(step && lr && hyper, "koaf_optim_hyper: bad args");
     hipLaunchKernelGGL(optim_hyper_kernel, dim3(1), dim3(1), 0, STREAM, step, lr, hyper);

@@ -208,8 +208,6 @@ __global__ void __launch_bounds__(256) stem_fwd_mma_kernel(const float* __restri
 }
 }  // namespace
 
-#define STREAM ((hipStream_t)stream)
-
 // rows of the statistics buffer: one per unit (image, band of SM_TH output rows)
 extern "C" int32_t koaf_stem_stats_rows(int32_t N, int32_t H) { return (int32_t)((int64_t)N * cdiv64(conv_out(H, 7, 2, 3), SM_TH)); }
 extern "C" int koaf_stem_fwd(const float* x, const float* w1t, float* y, int32_t N, int32_t H, int32_t W,
@@ -220,11 +218,11 @@ extern "C" int koaf_stem_fwd(const float* x, const float* w1t, float* y, int32_t
     KOAF_REQUIRE(units < (1ll << 31), "koaf_stem_fwd: grid too large");
     const dim3 grid((unsigned)(units < 512 ? units : 512));          // persistent: two blocks per CU
     if (stats) {
-        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, true>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
-        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, true>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, stats, stats_shift);
+        KOAF_LAUNCH_ACT16(act16, (stem_fwd_mma_kernel<A16, true>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, stats,
+                          stats_shift);
     } else {
-        if (act16) hipLaunchKernelGGL((stem_fwd_mma_kernel<true, false>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
-        else hipLaunchKernelGGL((stem_fwd_mma_kernel<false, false>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW, nullptr, nullptr);
+        KOAF_LAUNCH_ACT16(act16, (stem_fwd_mma_kernel<A16, false>), grid, dim3(256), 0, STREAM, x, w1t, y, N, H, W, OH, OW,
+                          nullptr, nullptr);
     }
     return koaf_check_launch("koaf_stem_fwd");
 }
@@ -475,10 +473,8 @@ extern "C" int koaf_stem_wgrad(const float* dy, const float* x, float* dw1t, int
     const int OH = conv_out(H, 7, 2, 3), OW = conv_out(W, 7, 2, 3);
     const int nb = stem_wgrad_blocks(N, H, W);
     if (dy_apply) {
-        if (act16) hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, true>), dim3(nb), dim3(256), 0, STREAM, dy_apply->dz, x, slabs, N, H, W, OH, OW,
-                                      dy_apply->c, dy_apply->coef);
-        else hipLaunchKernelGGL((stem_wgrad_mma_kernel<true, false>), dim3(nb), dim3(256), 0, STREAM, dy_apply->dz, x, slabs, N, H, W, OH, OW,
-                                dy_apply->c, dy_apply->coef);
+        KOAF_LAUNCH_ACT16(act16, (stem_wgrad_mma_kernel<true, A16>), dim3(nb), dim3(256), 0, STREAM, dy_apply->dz, x, slabs, N, H,
+                          W, OH, OW, dy_apply->c, dy_apply->coef);
     } else
         hipLaunchKernelGGL((stem_wgrad_mma_kernel<false, false>), dim3(nb), dim3(256), 0, STREAM, dy, x, slabs, N, H, W, OH, OW, nullptr, nullptr);
     const int rc = koaf_check_launch("koaf_stem_wgrad");
@@ -591,10 +587,8 @@ extern "C" int koaf_stem_dgrad(const float* dy, const float* w1t, float* dx, int
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)blocks);
     if (dy_apply) {
-        if (act16) hipLaunchKernelGGL((stem_dgrad_kernel<true, true>), grid, dim3(256), 0, st, dy_apply->dz, w1t, dx, H, W, OH, OW, tyn, txn,
-                                      dy_apply->c, dy_apply->coef);
-        else hipLaunchKernelGGL((stem_dgrad_kernel<true, false>), grid, dim3(256), 0, st, dy_apply->dz, w1t, dx, H, W, OH, OW, tyn, txn,
-                                dy_apply->c, dy_apply->coef);
+        KOAF_LAUNCH_ACT16(act16, (stem_dgrad_kernel<true, A16>), grid, dim3(256), 0, st, dy_apply->dz, w1t, dx, H, W, OH, OW, tyn,
+                          txn, dy_apply->c, dy_apply->coef);
     } else
         hipLaunchKernelGGL((stem_dgrad_kernel<false, false>), grid, dim3(256), 0, st, dy, w1t, dx, H, W, OH, OW, tyn, txn, nullptr, nullptr);
     return koaf_check_launch("koaf_stem_dgrad");

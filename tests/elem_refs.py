@@ -7,7 +7,7 @@ Bounds.  u = 2^-24 is the unit roundoff of fp32 round-to-nearest.
     counting a fused multiply-add as two roundings);
   * an fp32 sum whose longest chain of additions has length m errs by at most gamma(m) * sum|t_i|, gamma(m) = m u / (1 - m u)
     (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., eq. 4.4, any order of summation).
-The column kernels' m comes from the geometry below, a Python twin of col_geom (koaf_elem.hip), itself checked against
+The column kernels' m comes from the geometry below, a Python twin of col_geom (koaf_cols.h), itself checked against
 koaf_colpart_rows.
 """
 import math

@@ -1,4 +1,4 @@
-"""Element-wise parity of the HBM-bound kernels (koaf_elem.hip, the fused attention forward) at their edges: scalar tails,
+"""Element-wise parity of the HBM-bound kernels (koaf_bn.hip, koaf_rows.hip, koaf_preproc.hip, the fused attention forward) at their edges: scalar tails,
 the second trip of the grid-stride loops, the row growth and the width extremes of the column reductions, the one- / two-stage
 thresholds of the finalisations, max-pool borders and ties, softmax with large logits, both vector widths of the augmenter.
 
