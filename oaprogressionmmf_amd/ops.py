@@ -469,11 +469,12 @@ def stem_fwd(x, w1t, N, H, W, dtype=torch.float32, stats=False, shift=None):
     return (y, part) if stats else y
 
 
-def stem_wgrad(dy, x, dw, N, H, W):
-    """writes dw (packed [64,7,7,3] memory); dy may be a BnApply (the stem BatchNorm's backward, formed on load)"""
+def stem_wgrad(dy, x, dw, N, H, W, slabs=None):
+    """writes dw (packed [64,7,7,3] memory); dy may be a BnApply (the stem BatchNorm's backward, formed on load).
+    slabs (None = allocated here): the per-block slab workspace, at least koaf_stem_wgrad_ws floats."""
     L = lib()
     dyp, _, app, like = _dy_args(dy, None)
-    slabs = _empty((L.koaf_stem_wgrad_ws(N, H, W),), like)
+    slabs = _slab_ws(slabs, L.koaf_stem_wgrad_ws(N, H, W), like, "stem_wgrad")
     dw1t = _empty((49, 64), like)
     check(L.koaf_stem_wgrad(dyp, _ptr(x), _ptr(dw1t), N, H, W, _ptr(slabs), app, _a16(dy.c) if app is not None else 0, _stream()),
           "stem_wgrad")

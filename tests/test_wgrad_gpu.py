@@ -391,7 +391,8 @@ def test_weight_gradient_split_plans(dev, case):
 
 
 def test_slab_workspace_too_small_raises(dev):
-    """ops.conv2d_wgrad / ops.gconv3x3_wgrad refuse a `slabs=` workspace under koaf_conv2d_wgrad_ws / koaf_gconv3x3_wgrad_ws floats"""
+    """ops.conv2d_wgrad / ops.gconv3x3_wgrad / ops.stem_wgrad refuse a `slabs=` workspace under koaf_conv2d_wgrad_ws /
+    koaf_gconv3x3_wgrad_ws / koaf_stem_wgrad_ws floats"""
     from oaprogressionmmf_amd import _lib, ops
     N, H, W, Cin, Cout = 4, 16, 16, 64, 64
     x, dy = torch.zeros(N, H, W, Cin, device=dev), torch.zeros(N, H, W, Cout, device=dev)
@@ -402,3 +403,8 @@ def test_slab_workspace_too_small_raises(dev):
     wg = _lib.lib().koaf_gconv3x3_wgrad_ws(N, H, W, Cin, 1)
     with pytest.raises(_lib.KoafError):
         ops.gconv3x3_wgrad(dy, x, N, H, W, Cin, 1, slabs=torch.empty(wg - 1, device=dev))
+    wst = _lib.lib().koaf_stem_wgrad_ws(N, H, W)
+    assert wst > 0
+    with pytest.raises(_lib.KoafError):
+        ops.stem_wgrad(torch.zeros(N, H // 2, W // 2, 64, device=dev), torch.zeros(N, H, W, device=dev), torch.empty(64, 7, 7, 3, device=dev),
+                       N, H, W, slabs=torch.empty(wst - 1, device=dev))
