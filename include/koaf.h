@@ -753,6 +753,32 @@ int koaf_curve_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int
 int koaf_point_metrics(const void* scores, int32_t f64, int64_t stride, const int32_t* packed, int32_t n, double thr, double* out,
                        uint32_t* flag, void* stream);
 
+/* ---- paired permutation test of two models' ROC-AUC / average precision on the same samples (koaf_metrics.hip; the
+ * "Permutation testing" cell of run/Analysis_Visualization.ipynb: scipy.stats.permutation_test(permutation_type="samples") around
+ * metric(cmp) - metric(ref)).  A permutation swaps the two predictions of some samples.  That does not change the order of the
+ * union of the 2n scores, so the union is ranked once and each permutation is, per side, a histogram over the 2n rank bins; the
+ * labels do not move, so both sides of every row share P and N.  n <= KOAF_METRICS_MAX_N / 2 = 8192: the 2n bins are the
+ * histogram of the kernels above.  The arithmetic contract above holds unchanged: integer ranks, histograms, prefix sums and
+ * Mann-Whitney sums, fp64 sums in the fixed per-thread-run-then-tree order without fused multiply-add, no floating-point atomics,
+ * the same bits from run to run.  flag as above (bit 2: a rank of `packed` outside [0, 2n), which is skipped).
+ *
+ * koaf_pair_ranks  ranks the union s[j] = a[j * stride_a] (j < n), s[n + j] = b[j * stride_b], both columns fp32, or both fp64
+ *   when f64, compared in their own precision: rank[j] = #{ k < 2n : s[k] > s[j] }, so equal scores of the two models share a
+ *   bin.  packed[j] = rank[j] << 1 | (labels[j mod n] == pos_label) for j in [0, 2n); labels (int32 [n]) and packed go together,
+ *   rank is nullable when packed is given.
+ * koaf_perm_metrics  two blocks (one per side) per row of out [rows][8] fp64, rows = R + (with_identity ? 1 : 0).  masks is
+ *   uint32 [R][W], W = ceil(n / 32): row r' = r - with_identity swaps sample i when bit (i & 31) of word (i >> 5) is set; bits at
+ *   or beyond n are ignored; the identity row (row 0 when with_identity; masks may be NULL when R == 0) swaps nothing.  Side A
+ *   ("ref") counts packed[i] of an unswapped and packed[n + i] of a swapped sample, side B ("cmp") the other word.  With
+ *   (tp_g, fp_g) the positives / negatives of union bin g on a side:
+ *     out[r] = { P, N,  U_A, U_B,  ap_A, ap_B,  0, 0 },   U = sum_g fp_g * (2 * tp_before_g + tp_g)  (= 2 P N roc_auc, an integer
+ *     below 2^27, exact in fp64),   ap = sum_g (tp_g / P) * (tp / (tp + fp))
+ *   P == 0 or N == 0 writes the counts, and NaN for the four values U_A, U_B, ap_A, ap_B. */
+int koaf_pair_ranks(const void* a, int64_t stride_a, const void* b, int64_t stride_b, int32_t f64, int32_t n, const int32_t* labels,
+                    int32_t pos_label, int32_t* rank, int32_t* packed, uint32_t* flag, void* stream);
+int koaf_perm_metrics(const int32_t* packed, int32_t n, const uint32_t* masks, int32_t R, int32_t with_identity, double* out,
+                      uint32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

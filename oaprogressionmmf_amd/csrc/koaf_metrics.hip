@@ -3,6 +3,9 @@
 // resample then only changes how often each sample counts, so each resample is an integer histogram over the rank bins and one
 // ordered pass over it.  Everything that decides a result is integer arithmetic (LDS integer atomics, integer prefix sums, the
 // Mann-Whitney sum in int64); the fp64 sums run in a fixed order.  No floating-point atomics: run-to-run identical bits.
+// The paired permutation test of two models (scipy.stats.permutation_test(permutation_type="samples") around roc_auc_score /
+// average_precision_score differences) runs on the same pieces: swapping a sample's two predictions leaves the order of the
+// union of the 2n scores alone, so the union is ranked once and each permutation is a histogram over its 2n rank bins.
 #include "koaf_common.h"
 
 namespace {
@@ -43,11 +46,52 @@ __global__ void __launch_bounds__(MT_BLOCK) score_ranks_kernel(const T* __restri
     if (bad) atomicOr(flag, bad);
 }
 
-// ---- shared pieces of the two curve kernels ----------------------------------------------------------------------------------
+// the same over the union of two score columns: element j < n is a[j], element n + j is b[j]; both halves carry the labels of
+// the n samples.  A score of one model that equals a score of the other shares its rank bin.
+template <typename T>
+__global__ void __launch_bounds__(MT_BLOCK) pair_ranks_kernel(const T* __restrict__ a, int64_t stride_a, const T* __restrict__ b,
+                                                              int64_t stride_b, int n, const int32_t* __restrict__ labels,
+                                                              int pos_label, int32_t* __restrict__ rank,
+                                                              int32_t* __restrict__ packed, uint32_t* __restrict__ flag) {
+    __shared__ T tile[MT_TILE];
+    const int n2 = 2 * n;
+    const int i = blockIdx.x * MT_BLOCK + threadIdx.x;
+    const T mine = i < n ? a[(int64_t)i * stride_a] : i < n2 ? b[(int64_t)(i - n) * stride_b] : (T)0;
+    int cnt = 0;
+    for (int t0 = 0; t0 < n2; t0 += MT_TILE) {
+        const int len = n2 - t0 < MT_TILE ? n2 - t0 : MT_TILE;
+        __syncthreads();
+        for (int j = threadIdx.x; j < len; j += MT_BLOCK) {
+            const int k = t0 + j;
+            tile[j] = k < n ? a[(int64_t)k * stride_a] : b[(int64_t)(k - n) * stride_b];
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int j = 0; j < len; ++j) cnt += tile[j] > mine ? 1 : 0;
+    }
+    if (i >= n2) return;
+    unsigned bad = 0;
+    if (!(fabs((double)mine) <= 1.7976931348623157e308)) bad |= 1u;          // NaN / Inf
+    if (rank) rank[i] = cnt;
+    if (labels) {
+        const int32_t l = labels[i < n ? i : i - n];
+        if (l != 0 && l != 1) bad |= 2u;
+        packed[i] = (cnt << 1) | (l == pos_label ? 1 : 0);
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+// ---- shared pieces of the curve kernels ----------------------------------------------------------------------------------
 // A histogram word holds the bin's positives in its upper and its negatives in its lower 16 bits: at most m <= 16384 draws per
 // resample, so neither half can carry.
 __device__ __forceinline__ int h_tp(uint32_t w) { return (int)(w >> 16); }
 __device__ __forceinline__ int h_fp(uint32_t w) { return (int)(w & 0xffffu); }
+
+// one draw into its bin.  A rank outside [0, bins) is not followed: it raises flag bit 2.
+__device__ __forceinline__ void hist_add(uint32_t* hist, int32_t w, int bins, uint32_t* flag) {
+    if ((unsigned)(w >> 1) >= (unsigned)bins) { atomicOr(flag, 4u); return; }         // (not a word the rank kernels wrote for this n)
+    atomicAdd(&hist[w >> 1], (w & 1) ? 0x10000u : 1u);
+}
 
 // zero the n bins, then add the m draws of this resample (idx row, or the identity when idx is NULL).  An index or a rank
 // outside [0, n) is not followed: it raises flag bit 2.
@@ -58,9 +102,20 @@ __device__ __forceinline__ void fill_hist(uint32_t* hist, const int32_t* __restr
     for (int k = threadIdx.x; k < m; k += MT_BLOCK) {
         const int i = idx ? idx[k] : k;
         if ((unsigned)i >= (unsigned)n) { atomicOr(flag, 4u); continue; }
-        const int32_t w = packed[i];
-        if ((unsigned)(w >> 1) >= (unsigned)n) { atomicOr(flag, 4u); continue; }      // (not a word koaf_score_ranks wrote for this n)
-        atomicAdd(&hist[w >> 1], (w & 1) ? 0x10000u : 1u);
+        hist_add(hist, packed[i], n, flag);
+    }
+    __syncthreads();
+}
+
+// the same for one side of a paired permutation: sample i counts with its own word (packed[i] on side 0, packed[n + i] on side
+// 1) unless bit i of the mask row is set, then with the other model's.  row == NULL: nothing is swapped.  2n bins.
+__device__ __forceinline__ void fill_hist_swapped(uint32_t* hist, const int32_t* __restrict__ packed, int n,
+                                                  const uint32_t* __restrict__ row, int side, uint32_t* flag) {
+    for (int g = threadIdx.x; g < 2 * n; g += MT_BLOCK) hist[g] = 0u;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += MT_BLOCK) {
+        const int swapped = row ? (int)((row[i >> 5] >> (i & 31)) & 1u) : 0;
+        hist_add(hist, packed[(side ^ swapped) ? n + i : i], 2 * n, flag);
     }
     __syncthreads();
 }
@@ -83,6 +138,31 @@ __device__ __forceinline__ void run_prefix(const uint32_t* hist, int n, int* s_t
         if (t < (int)threadIdx.x) { tp_before += a; fp_before += b; }
         P += a;
         N += b;
+    }
+}
+
+// the ordered walk of one thread over the non-empty bins of its run [g0, g1) (descending score = ascending rank); tp / fp come in
+// as the counts ahead of the run.  auc: the Mann-Whitney sum sum_g fp_g (2 tp_before_g + tp_g); ap: sum_g (tp_g / P) tp / (tp + fp);
+// cal (CAL only): the same with the negatives weighted by `ratio`.
+template <bool CAL>
+__device__ __forceinline__ void walk_run(const uint32_t* hist, int g0, int g1, int tp, int fp, double dP, double ratio,
+                                         long long& auc, double& ap, double& cal) {
+#pragma clang fp contract(off)
+    for (int g = g0; g < g1; ++g) {
+        const uint32_t w = hist[g];
+        if (w == 0u) continue;
+        const int tg = h_tp(w), fg = h_fp(w);
+        auc += (long long)fg * (long long)(2 * tp + tg);
+        tp += tg;
+        fp += fg;
+        if (tg != 0) {
+            const double dr = (double)tg / dP, dtp = (double)tp;
+            ap += dr * (dtp / (double)(tp + fp));
+            if (CAL) {
+                const double den = dtp + ratio * (double)fp;
+                cal += dr * (den == 0.0 ? 0.0 : dtp / den);
+            }
+        }
     }
 }
 
@@ -114,22 +194,7 @@ __global__ void __launch_bounds__(MT_BLOCK) curve_metrics_kernel(const int32_t* 
     const double ratio = pi * (1.0 - pi0) / (pi0 * (1.0 - pi));           // (_metrics_wissam.py:151-152, in its order)
     long long auc = 0;
     double ap = 0.0, cal = 0.0;
-    if (P > 0 && N > 0) {
-        for (int g = g0; g < g1; ++g) {
-            const uint32_t w = hist[g];
-            if (w == 0u) continue;
-            const int tg = h_tp(w), fg = h_fp(w);
-            auc += (long long)fg * (long long)(2 * tp + tg);
-            tp += tg;
-            fp += fg;
-            if (tg != 0) {
-                const double dr = (double)tg / dP, dtp = (double)tp;
-                ap += dr * (dtp / (double)(tp + fp));
-                const double den = dtp + ratio * (double)fp;
-                cal += dr * (den == 0.0 ? 0.0 : dtp / den);
-            }
-        }
-    }
+    if (P > 0 && N > 0) walk_run<true>(hist, g0, g1, tp, fp, dP, ratio, auc, ap, cal);
     r_auc[threadIdx.x] = auc;
     r_ap[threadIdx.x] = ap;
     r_cal[threadIdx.x] = cal;
@@ -152,6 +217,53 @@ __global__ void __launch_bounds__(MT_BLOCK) curve_metrics_kernel(const int32_t* 
         o[3] = ok ? r_ap[0] : nan;
         o[4] = ok ? r_cal[0] : nan;
         o[5] = o[6] = o[7] = 0.0;
+    }
+}
+
+// ---- paired permutation test of two models ----------------------------------------------------------------------------------
+// Block (r, side): the histogram over the 2n union bins of what permutation r leaves on that side (0: "ref", 1: "cmp"), the same
+// walk and tree.  The labels do not move, so both sides of every row hold the same P and N.  out[r][0..8): P, N, U of side 0,
+// U of side 1, avg_precision of side 0, of side 1, 0, 0 -- U the Mann-Whitney sum itself (2 P N roc_auc), an integer < 2^27.
+template <int BINS>
+__global__ void __launch_bounds__(MT_BLOCK) perm_metrics_kernel(const int32_t* __restrict__ packed, int n,
+                                                                const uint32_t* __restrict__ masks, int W, int with_identity,
+                                                                double* __restrict__ out, uint32_t* __restrict__ flag) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t hist[BINS];
+    __shared__ int s_tp[MT_BLOCK], s_fp[MT_BLOCK];
+    __shared__ long long r_auc[MT_BLOCK];
+    __shared__ double r_ap[MT_BLOCK];
+    const int r = blockIdx.x, side = blockIdx.y;
+    const uint32_t* row = nullptr;
+    if (masks != nullptr && !(with_identity && r == 0)) row = masks + (int64_t)(r - (with_identity ? 1 : 0)) * W;
+    fill_hist_swapped(hist, packed, n, row, side, flag);
+    int g0, g1, tp, fp, P, N;
+    run_prefix(hist, 2 * n, s_tp, s_fp, g0, g1, tp, fp, P, N);
+    const double dP = (double)P, dN = (double)N;
+    long long auc = 0;
+    double ap = 0.0, cal = 0.0;
+    if (P > 0 && N > 0) walk_run<false>(hist, g0, g1, tp, fp, dP, 0.0, auc, ap, cal);
+    r_auc[threadIdx.x] = auc;
+    r_ap[threadIdx.x] = ap;
+    __syncthreads();
+    for (int o = MT_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            r_auc[threadIdx.x] += r_auc[threadIdx.x + o];
+            r_ap[threadIdx.x] += r_ap[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double* o = out + (int64_t)r * 8;
+        const bool ok = P > 0 && N > 0;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        if (side == 0) {
+            o[0] = dP;
+            o[1] = dN;
+            o[6] = o[7] = 0.0;
+        }
+        o[2 + side] = ok ? (double)r_auc[0] : nan;
+        o[4 + side] = ok ? r_ap[0] : nan;
     }
 }
 
@@ -268,6 +380,42 @@ extern "C" int koaf_curve_metrics(const int32_t* packed, int32_t n, const int32_
     else
         hipLaunchKernelGGL(curve_metrics_kernel<MT_MAX_N>, grid, block, 0, STREAM, packed, n, ix, m, with_identity, pi0, out, flag);
     return koaf_check_launch("koaf_curve_metrics");
+}
+
+extern "C" int koaf_pair_ranks(const void* a, int64_t stride_a, const void* b, int64_t stride_b, int32_t f64, int32_t n,
+                               const int32_t* labels, int32_t pos_label, int32_t* rank, int32_t* packed, uint32_t* flag,
+                               void* stream) {
+    KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N / 2, "koaf_pair_ranks: 1 <= n <= %d (n = %d)", MT_MAX_N / 2, n);
+    KOAF_REQUIRE(stride_a >= 1 && stride_a < (1ll << 32) && stride_b >= 1 && stride_b < (1ll << 32),
+                 "koaf_pair_ranks: 1 <= stride < 2^32 (strides = %lld, %lld)", (long long)stride_a, (long long)stride_b);
+    KOAF_REQUIRE(a && b && flag && (rank || packed), "koaf_pair_ranks: both score columns, flag and one of rank / packed are required");
+    KOAF_REQUIRE((labels != nullptr) == (packed != nullptr), "koaf_pair_ranks: labels and packed go together");
+    const dim3 grid((unsigned)cdiv64(2 * n, MT_BLOCK)), block(MT_BLOCK);
+    if (f64)
+        hipLaunchKernelGGL(pair_ranks_kernel<double>, grid, block, 0, STREAM, (const double*)a, stride_a, (const double*)b, stride_b,
+                           n, labels, pos_label, rank, packed, flag);
+    else
+        hipLaunchKernelGGL(pair_ranks_kernel<float>, grid, block, 0, STREAM, (const float*)a, stride_a, (const float*)b, stride_b, n,
+                           labels, pos_label, rank, packed, flag);
+    return koaf_check_launch("koaf_pair_ranks");
+}
+
+extern "C" int koaf_perm_metrics(const int32_t* packed, int32_t n, const uint32_t* masks, int32_t R, int32_t with_identity,
+                                 double* out, uint32_t* flag, void* stream) {
+    KOAF_REQUIRE(n >= 1 && n <= MT_MAX_N / 2, "koaf_perm_metrics: 1 <= n <= %d (n = %d)", MT_MAX_N / 2, n);
+    KOAF_REQUIRE(packed && out && flag, "koaf_perm_metrics: packed, out and flag are required");
+    KOAF_REQUIRE(R >= 0 && R <= (1 << 20), "koaf_perm_metrics: 0 <= R <= 2^20 (R = %d)", R);
+    KOAF_REQUIRE(masks != nullptr || R == 0, "koaf_perm_metrics: R = %d permutations need a mask matrix", R);
+    const int rows = R + (with_identity ? 1 : 0);
+    KOAF_REQUIRE(rows >= 1, "koaf_perm_metrics: nothing to do (R = 0 and no identity row)");
+    const dim3 grid((unsigned)rows, 2), block(MT_BLOCK);
+    const uint32_t* mk = R > 0 ? masks : nullptr;
+    const int W = (n + 31) / 32;
+    if (2 * n <= 4096)
+        hipLaunchKernelGGL(perm_metrics_kernel<4096>, grid, block, 0, STREAM, packed, n, mk, W, with_identity, out, flag);
+    else
+        hipLaunchKernelGGL(perm_metrics_kernel<MT_MAX_N>, grid, block, 0, STREAM, packed, n, mk, W, with_identity, out, flag);
+    return koaf_check_launch("koaf_perm_metrics");
 }
 
 extern "C" int koaf_point_metrics(const void* scores, int32_t f64, int64_t stride, const int32_t* packed, int32_t n, double thr,

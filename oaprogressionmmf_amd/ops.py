@@ -734,7 +734,7 @@ def attr_fold(acc, g, w, square=False, first=False, x=None, base=None):
 # ------------------------------------------------------------------------------------------------
 METRICS_MAX_N = defines()["KOAF_METRICS_MAX_N"]
 METRICS_FLAG_TEXT = {1: "Input contains NaN or infinity.", 2: "a label other than 0 / 1 (binary targets only)",
-                     4: "an index of the resampling matrix lies outside [0, n)"}
+                     4: "an index of the resampling matrix lies outside [0, n)"}      # (or a rank of `packed` outside its bins)
 
 
 def metrics_flag(device):
@@ -836,6 +836,69 @@ def point_metrics(scores, packed, thr=0.5, out=None, flag=None):
     _metric_i32("point_metrics", "flag", flag, scores, (1,))
     check(lib().koaf_point_metrics(_ptr(scores), 1 if scores.dtype == torch.float64 else 0, stride, _ptr(packed), n, float(thr),
                                    _ptr(out), _ptr(flag), _stream()), "point_metrics")
+    if own:
+        metrics_raise(flag.item())
+    return out
+
+
+def pair_ranks(scores_a, scores_b, labels=None, pos_label=1, flag=None):
+    """score_ranks over the UNION of two score columns of the same n samples (koaf_pair_ranks): element j < n is scores_a[j],
+    element n + j is scores_b[j]; rank[j] = #{k : union[k] > union[j]} (int32 [2n]), so equal scores of the two models share a
+    rank.  Both columns are 1-D device vectors of one dtype (fp32 or fp64), each read through its own positive stride,
+    n <= METRICS_MAX_N // 2.  With labels (int32 [n]) also packed[j] = rank[j] << 1 | (labels[j mod n] == pos_label), what
+    perm_metrics reads: -> (rank, packed).  flag as in score_ranks."""
+    n, stride_a = _metric_scores("pair_ranks", scores_a)
+    nb, stride_b = _metric_scores("pair_ranks", scores_b)
+    if nb != n or scores_b.dtype != scores_a.dtype or scores_b.device != scores_a.device:
+        raise KoafError(f"pair_ranks: two columns of one length, dtype and device, got {n} {scores_a.dtype} {scores_a.device} and "
+                        f"{nb} {scores_b.dtype} {scores_b.device}")
+    if labels is not None:
+        _metric_i32("pair_ranks", "labels", labels, scores_a, (n,))
+    own = flag is None
+    if own:
+        flag = metrics_flag(scores_a.device)
+    _metric_i32("pair_ranks", "flag", flag, scores_a, (1,))
+    rank = torch.empty(2 * n, dtype=torch.int32, device=scores_a.device)
+    packed = torch.empty(2 * n, dtype=torch.int32, device=scores_a.device) if labels is not None else None
+    check(lib().koaf_pair_ranks(_ptr(scores_a), stride_a, _ptr(scores_b), stride_b, 1 if scores_a.dtype == torch.float64 else 0, n,
+                                _ptr(labels), int(pos_label), _ptr(rank), _ptr(packed), _ptr(flag), _stream()), "pair_ranks")
+    if own:
+        metrics_raise(flag.item())
+    return rank if labels is None else (rank, packed)
+
+
+def perm_metrics(packed, masks=None, with_identity=True, out=None, flag=None):
+    """out [rows, 8] fp64, row r = (n_pos, n_neg, U_ref, U_cmp, ap_ref, ap_cmp, 0, 0) of one paired permutation of the n samples
+    behind packed (pair_ranks, int32 [2n]): row 0 the sample as it is when with_identity, then one row per row of masks (int32
+    [R, ceil(n / 32)] device words holding the bits of a uint32 matrix: sample i changes sides when bit i & 31 of word i >> 5 is
+    set; None: no permutations).  U is the Mann-Whitney sum 2 * n_pos * n_neg * roc_auc as an exact integer, ap the average
+    precision (koaf_perm_metrics: two blocks per row, integer histograms over the 2n union bins, fixed-order fp64 sums --
+    identical bits from run to run).  flag as in score_ranks."""
+    if not torch.is_tensor(packed) or not packed.is_cuda:
+        raise KoafError("perm_metrics: packed is the device tensor pair_ranks returns")
+    _metric_i32("perm_metrics", "packed", packed, packed)
+    if packed.dim() != 1 or packed.numel() == 0 or packed.numel() % 2:
+        raise KoafError(f"perm_metrics: packed holds 2n words, got {tuple(packed.shape)}")
+    n = int(packed.numel()) // 2
+    R = 0
+    if masks is not None:
+        _metric_i32("perm_metrics", "masks", masks, packed)
+        if masks.dim() != 2 or masks.numel() == 0 or int(masks.shape[1]) != (n + 31) // 32:
+            raise KoafError(f"perm_metrics: masks is a non-empty [R, {(n + 31) // 32}] matrix, got {tuple(masks.shape)}")
+        R = int(masks.shape[0])
+    rows = R + (1 if with_identity else 0)
+    if rows == 0:
+        raise KoafError("perm_metrics: neither the identity row nor a mask matrix")
+    if out is None:
+        out = torch.empty((rows, 8), dtype=torch.float64, device=packed.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (rows, 8) or out.device != packed.device:
+        raise KoafError(f"perm_metrics: out is contiguous fp64 [{rows}, 8] on packed's device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(packed.device)
+    _metric_i32("perm_metrics", "flag", flag, packed, (1,))
+    check(lib().koaf_perm_metrics(_ptr(packed), n, _ptr(masks), R, 1 if with_identity else 0, _ptr(out), _ptr(flag), _stream()),
+          "perm_metrics")
     if own:
         metrics_raise(flag.item())
     return out
