@@ -318,6 +318,27 @@ static inline bool wgrad3_ring_shape(int N, int H, int W, int Cin, int Cout, int
     return KH == 3 && KW == 3 && stride == 1 && pad == 1 && koaf_wgrad3_ring_ok(N, H, W, Cin, Cout);
 }
 
+// koaf_wgrad1.hip: 1x1 / stride 1 over the fp32 tensors on 256-wide tiles, same split-K plan and slabs
+int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream);
+// the tile on which koaf_wgrad1 takes the weight gradient described by g under plan p (bm = 0: the generic kernel keeps it): the fp16
+// scheme on fp32 tensors, channel counts in whole tiles of 128 with at least one side 256 wide, and k-ranges of at least WGRAD1_MIN_KCHUNK
+// pixels -- shorter launches stay with the generic kernel's more and smaller blocks
+constexpr int WGRAD1_MIN_KCHUNK = 1024;
+static inline WgradPlan wgrad1_tile(const KoafGemm& g, const WgradPlan& p, bool pointwise) {
+    WgradPlan t = {0, 0, p.splitk};
+    if (!pointwise || g.fmt != 1 || g.act16 != 0 || g.A.kind != 1 || g.B.kind != 1) return t;
+    if (g.M % 128 || g.N % 128 || (g.M < 256 && g.N < 256)) return t;
+    const int bm = g.M >= 256 ? 256 : 128, bn = g.N >= 256 ? 256 : 128;
+    if (g.M % bm || g.N % bn) return t;
+    if (rup32(cdiv64(g.K, p.splitk)) < WGRAD1_MIN_KCHUNK) return t;
+    // (what koaf_gemm's vector path asks of the pointers; an unaligned call takes the generic kernel's scalar path)
+    if (!aligned16(g.A.ptr) || !aligned16(g.B.ptr) || !aligned16(g.C)) return t;
+    if (g.A.tf && (!aligned16(g.A.ptr2) || !aligned16(g.A.sc) || !aligned16(g.A.sh) || !aligned16(g.A.sc2))) return t;
+    if (g.B.tf && (!aligned16(g.B.sc) || !aligned16(g.B.sh))) return t;
+    t.bm = bm; t.bn = bn;
+    return t;
+}
+
 extern "C" int64_t koaf_conv2d_wgrad_ws(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
                                         int32_t KW, int32_t stride, int32_t pad) {
     const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
@@ -375,7 +396,8 @@ extern "C" int koaf_conv2d_wgrad(const float* dy, const float* x, float* dw, int
     g.C = p.splitk > 1 ? slabs : dw;
     g.ldc = Ntot;
     g.act16 = (act16 && !dy_planes) ? 3 : 0;      // (x and dy_apply->c are bf16 activations; plane images carry no storage type)
-    int rc = koaf_gemm(&g, stream);
+    const WgradPlan t1 = wgrad1_tile(g, p, is_pointwise(KH, KW, stride, pad));
+    int rc = t1.bm ? koaf_wgrad1(g, t1.bm, t1.bn, stream) : koaf_gemm(&g, stream);
     if (rc != KOAF_OK || p.splitk == 1) return rc;
     return koaf_slab_reduce(slabs, p.splitk, (int64_t)Cout * Ntot, dw, stream);
 }

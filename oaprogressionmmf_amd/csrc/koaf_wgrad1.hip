@@ -1,0 +1,285 @@
+// koaf_wgrad1.hip -- weight gradient of the 1x1 / stride-1 convolutions on 256-wide tiles (k = pixel):
+//     dw[co][ci] = sum_p dc[p][co] * x~[p][ci]
+// with both operands K-major fp32 in HBM and the transforms of koaf_gemm's loaders formed on load: dc = dy, or the BatchNorm-backward
+// apply k0 dz + k3 - k2 c of two sources (KoafOperand.tf 2); x~ = x, or relu(in_sc x + in_sh) (tf 1).  fp16 scheme only
+// (KoafGemm.fmt 1: two fp16 pieces per value, three MFMAs per product).
+// The generic kernel (koaf_gemm_kernel, M_KM x M_KM) runs these calls on 128 x 128 tiles with ONE LDS image per operand and two
+// block barriers per 32-pixel k-step: the apply / prologue, the piece split and the LDS store sit between the barriers with the
+// matrix pipe idle, and every element of an operand is converted once per tile of the OTHER dimension.  Here a block of 512 threads
+// (waves 4 x 2) owns a 256 x 256 tile (256 x 128 / 128 x 256 where a dimension is 128 wide) -- half the conversions and half the L2
+// reads per operand element -- with two LDS stages per operand and one barrier per k-step:
+//     step s:  MFMAs of k-tile s (stage s % 2)  ||  convert + split + store of k-tile s + 1 (registers -> stage (s + 1) % 2),
+//              each register unit refilled with its loads of k-tile s + 2 as soon as it is converted
+// so a load has a whole k-step to land and the vector work runs in the shadow of the matrix instructions (its own wave's and
+// those of the second wave on the SIMD).  Register slots are static (one k-tile in registers, unit by unit); the loads behind the
+// end of the k-range are issued unconditionally, clamped into the tensor, into registers whose conversion nobody reads.
+// Every wave executes every barrier; there is no role split, no spin-wait and no hand-off between blocks.
+// Arithmetic, pieces, LDS images (plane[k][ROWS + 32 pad], koaf_pieces.h) and the order of the piece products per accumulator and
+// 16-k slice are those of TileLoader + koaf_gemm_kernel's mma(): slabs and dw are bit-identical to the generic path
+// (tests/test_wgrad1x1_gpu.py).  Split-K plan, slab layout and the XCD remap are koaf_gemm's.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+#include "koaf.h"
+#include "koaf_pieces.h"
+
+namespace {
+struct Wg1Params {
+    const float* a;        // dy (tf 0) or dz (tf 2), [K][M]
+    const float* a2;       // tf 2: the conv output c, same layout
+    const float* asc;      // tf 2: k0, k3, k2 per output channel (KoafOperand.sc / sh / sc2)
+    const float* ash;
+    const float* asc2;
+    const float* a_amax;   // scale of A = scale_of_amax(*a_amax)
+    const float* b;        // x, [K][N]
+    const float* bsc;      // tf 1: in_sc / in_sh per input channel
+    const float* bsh;
+    float b_scale;         // scale of B (fixed)
+    float* out;            // slabs [splitk][M][N], or dw [M][N] when splitk == 1
+    uint32_t* status;
+    int M, N, K, splitk;
+};
+
+constexpr int WG1_NT = 512;
+
+// one K-major fp32 operand of the block: R columns of the 32 rows of a k-tile, 4 columns x (R / 64) rows ("units") per thread
+template <int R, int TF>
+struct Wg1Loader {
+    static constexpr int NU = R / 64;                 // units per thread and k-tile
+    static constexpr int CV = R / 4;                  // threads across a k-row
+    static constexpr int RP = WG1_NT / CV;            // k-rows per pass of the block
+    static constexpr int SK = R / 2 + 16;             // dwords per k-row of a plane image
+    static constexpr int PL = plane_dwords(R, false);
+    v4f r[NU];
+    v4f r2[TF == 2 ? NU : 1];
+    v4f ca, cb, ck;        // transform coefficients of this thread's four columns, scaled
+    const float* src;
+    const float* src2;
+    float fsc;
+    unsigned ld, col, kr;
+
+    __device__ __forceinline__ void init(const float* p, const float* p2, const float* sc, const float* sh, const float* sc2,
+                                         int c0, int ldim, float scale) {
+        const unsigned t = threadIdx.x;
+        src = p; src2 = p2;
+        fsc = scale;
+        ld = (unsigned)ldim;
+        col = (unsigned)c0 + 4u * (t % CV);
+        kr = t / CV;
+        ca = cb = ck = (v4f){0.f, 0.f, 0.f, 0.f};
+        if constexpr (TF != 0) {
+            ca = *(const v4f*)(sc + col) * fsc;
+            cb = *(const v4f*)(sh + col) * fsc;
+            if constexpr (TF == 2) ck = *(const v4f*)(sc2 + col) * fsc;
+        }
+    }
+    // loads of unit i of the k-tile at k0 (any k0 >= 0: rows past the tensor's last re-read it)
+    __device__ __forceinline__ void issue(int i, int k0, int K) {
+        const int kb = min(k0, K - 1);                                  // (block-uniform)
+        const unsigned rowmax = (unsigned)(K - 1 - kb);
+        const unsigned row = min(kr + (unsigned)(RP * i), rowmax);
+        const unsigned off = __umul24(row, ld) + col;                  // (< 32 * 2^16: the tile's base is added as a 64-bit scalar)
+        const int64_t base = (int64_t)kb * ld;
+        r[i] = *(const v4f*)(src + base + off);
+        if constexpr (TF == 2) r2[i] = *(const v4f*)(src2 + base + off);
+    }
+    // TileLoader::finish_unit's arithmetic + split2h + the store of TileLoader::store, for unit i of the k-tile whose klim first
+    // rows lie inside the k-range
+    template <bool FULL>
+    __device__ __forceinline__ void convert(int i, int klim, unsigned* S) {
+        constexpr float HMAX = 65504.f;
+        const bool ok = FULL || (int)(kr + (unsigned)(RP * i)) < klim;
+        v4f v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x = r[i][j];
+            if constexpr (TF == 1) {
+                x = fmaf(x, ca[j], cb[j]);
+                x = __builtin_amdgcn_fmed3f(x, 0.f, HMAX);
+            } else if constexpr (TF == 2) {
+                x = fmaf(ca[j], x, fmaf(-ck[j], r2[i][j], cb[j]));
+                x = __builtin_amdgcn_fmed3f(x, -HMAX, HMAX);
+            } else {
+                x = __builtin_amdgcn_fmed3f(x * fsc, -HMAX, HMAX);
+            }
+            v[j] = ok ? x : 0.f;
+        }
+        unsigned pl[2][2];
+        split2h(v, pl);
+        const unsigned off = (kr + (unsigned)(RP * i)) * SK + 2u * (threadIdx.x % CV);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) *(uint2*)&S[q * PL + off] = make_uint2(pl[q][0], pl[q][1]);
+    }
+};
+
+template <int BM, int BN, int TFA, int TFB>
+__global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
+    constexpr int WGM = 4, WGN = 2;                                   // waves along M x N
+    constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 32, TN = WN / 32;
+    typedef Wg1Loader<BM, TFA> LA;
+    typedef Wg1Loader<BN, TFB> LB;
+    constexpr int A_ELEMS = 2 * LA::PL, B_ELEMS = 2 * LB::PL, STAGE = A_ELEMS + B_ELEMS;
+    static_assert(2 * STAGE * 4 <= 160 * 1024, "two stages of both operands in LDS");
+    __shared__ __attribute__((aligned(16))) unsigned smem[2 * STAGE];
+
+    // block -> (k-range, tile): koaf_gemm_kernel's split-K remap -- XCD = linear id % 8 takes the splits = x (mod 8), all tiles of a
+    // split in consecutive slots of one XCD (one L2)
+    const int ntn = p.N / BN;
+    unsigned bid = blockIdx.x;
+    int split = blockIdx.y;
+    if (gridDim.y > 1 && (gridDim.y & 7) == 0) {
+        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y, x = lin & 7, slot = lin >> 3;
+        bid = slot % gridDim.x;
+        split = (int)((slot / gridDim.x) * 8 + x);
+    }
+    const int tn = bid % ntn, tm = bid / ntn;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int kchunk = (((p.K + p.splitk - 1) / p.splitk + BK - 1) / BK) * BK;
+    const int kbeg = split * kchunk;
+    const int kend = min(p.K, kbeg + kchunk);
+    const int klen = max(kend - kbeg, 0), nstep = (klen + BK - 1) / BK;
+
+    const float sca = scale_of_amax(*p.a_amax), scb = p.b_scale;
+    float alpha = 1.f / (sca * scb);
+    if (!koaf_bits_finite(koaf_absbits(*p.a_amax))) {
+        alpha = __uint_as_float(0x7fc00000u);          // (a diverged dy: the whole gradient is NaN, as koaf_gemm does)
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) koaf_status_add(p.status, 1, 1u);
+    }
+
+    LA la;
+    LB lb;
+    la.init(p.a, p.a2, p.asc, p.ash, p.asc2, m0, p.M, sca);
+    lb.init(p.b, nullptr, p.bsc, p.bsh, nullptr, n0, p.N, scb);
+
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wm = w / WGN, wn = w % WGN;
+
+    v16f acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    // conversion unit u of the k-tile in registers (A units first) into the stage at S, then the unit's loads of the k-tile at k2
+    constexpr int NUT = LA::NU + LB::NU, NG = 2 * TN;                 // units per k-tile; MFMA groups (16-k slice x column tile) per k-step
+    auto unit = [&](auto full, int u, int klim, unsigned* S, int k2) {
+        constexpr bool FULL = decltype(full)::value;
+        if (u < LA::NU) {
+            la.template convert<FULL>(u, klim, S);
+            la.issue(u, k2, p.K);
+        } else {
+            lb.template convert<FULL>(u - LA::NU, klim, S + A_ELEMS);
+            lb.issue(u - LA::NU, k2, p.K);
+        }
+    };
+    // k-step: the MFMAs of the stage at cur -- per accumulator the order of koaf_gemm_kernel's mma(): 16-k slice g, then lo*hi, hi*lo,
+    // hi*hi -- with the units of the next k-tile dealt out behind its MFMA groups
+    auto step = [&](auto full, int cur, int klim, int k2) {
+        const unsigned* Au = smem + cur * STAGE;
+        const unsigned* Bu = Au + A_ELEMS;
+        unsigned* Sn = smem + (cur ^ 1) * STAGE;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            v4i ap[TM][2];
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) ap[i][q] = frag_load<BM, false>(Au + q * LA::PL, wm * WM + 32 * i, g, lane);
+#pragma unroll
+            for (int jn = 0; jn < TN; ++jn) {
+                v4i bp[2];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) bp[q] = frag_load<BN, false>(Bu + q * LB::PL, wn * WN + 32 * jn, g, lane);
+                constexpr int PAH[3] = {1, 0, 0}, PBH[3] = {0, 1, 0};
+#pragma unroll
+                for (int term = 0; term < 3; ++term)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ap[i][PAH[term]]),
+                                                                            __builtin_bit_cast(h16x8, bp[PBH[term]]), acc[i][jn], 0, 0, 0);
+                const int grp = g * TN + jn;
+#pragma unroll
+                for (int u = 0; u < NUT; ++u)
+                    if (u * NG / NUT == grp) unit(full, u, klim, Sn, k2);
+                // the scheduler keeps each group's MFMAs, vector work and loads where they are written (only fragment reads and scalar
+                // work may cross): left free, it sinks every global load to the end of the step, in front of its first use
+                __builtin_amdgcn_sched_barrier(0x104);
+            }
+        }
+        // every wave is done reading this stage and has written its part of the next (the loads stay in flight)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+
+    if (nstep > 0) {
+#pragma unroll
+        for (int i = 0; i < LA::NU; ++i) la.issue(i, kbeg, p.K);
+#pragma unroll
+        for (int i = 0; i < LB::NU; ++i) lb.issue(i, kbeg, p.K);
+#pragma unroll
+        for (int u = 0; u < NUT; ++u) unit(std::false_type{}, u, klen, smem, kbeg + BK);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+    // steps whose NEXT k-tile lies wholly inside the range convert without zero fill
+    const int nfull = max(klen / BK - 1, 0);
+    int s = 0;
+#pragma unroll 1
+    for (; s < nfull; ++s) step(std::true_type{}, s & 1, BK, kbeg + (s + 2) * BK);
+#pragma unroll 1
+    for (; s < nstep; ++s) step(std::false_type{}, s & 1, klen - (s + 1) * BK, kbeg + (s + 2) * BK);
+
+    // ---- partial tile -> slab (dw itself when splitk == 1): v = alpha * acc, plus the zero bias the shared epilogue adds ----
+    float* out = p.out + (p.splitk > 1 ? (int64_t)split * p.M * p.N : (int64_t)0);
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int jn = 0; jn < TN; ++jn)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float v = alpha * acc[i][jn][e];
+                asm volatile("" : "+v"(v));            // (the product is rounded before the add, as through the staging tile)
+                v += 0.f;
+                const int row = m0 + wm * WM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
+                const int col = n0 + wn * WN + 32 * jn + r;
+                out[(int64_t)row * p.N + col] = v;
+            }
+}
+
+template <int BM, int BN>
+int wg1_launch(const Wg1Params& p, int tfa, int tfb, dim3 grid, hipStream_t s) {
+#define WG1_GO(TA, TB) hipLaunchKernelGGL((wgrad1_kernel<BM, BN, TA, TB>), grid, dim3(WG1_NT), 0, s, p)
+    if (tfa == 2) { if (tfb) WG1_GO(2, 1); else WG1_GO(2, 0); }
+    else { if (tfb) WG1_GO(0, 1); else WG1_GO(0, 0); }
+#undef WG1_GO
+    return koaf_check_launch("koaf_wgrad1");
+}
+}  // namespace
+
+void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
+
+// the 1x1 / stride-1 weight gradient described by g (koaf_conv2d_wgrad's descriptor: A = dy [K][M] K-major with tf 0 | 2, B = x [K][N]
+// K-major with tf 0 | 1, fmt 1, act16 0, C = slabs or dw) on bm x bn tiles; the caller has checked the dispatch rule (koaf_conv.hip wgrad1_tile)
+int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream) {
+    KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && g.A.kind == 1 && g.B.kind == 1 && !g.A.gather && !g.B.gather && g.A.amax && g.A.ptr && g.B.ptr &&
+                 g.C && (g.A.tf == 0 || (g.A.tf == 2 && g.A.ptr2 && g.A.sc && g.A.sh && g.A.sc2)) && (g.B.tf == 0 || (g.B.tf == 1 && g.B.sc && g.B.sh)) &&
+                 (bm == 256 || bm == 128) && (bn == 256 || bn == 128) && bm + bn >= 384 && g.M % bm == 0 && g.N % bn == 0 && g.K >= BK && g.K < (1 << 30) &&
+                 g.splitk >= 1 && g.splitk <= 65535 && g.A.ld == g.M && g.B.ld == g.N && g.ldc == g.N,
+                 "koaf_wgrad1: bad args");
+    Wg1Params p;
+    p.a = g.A.ptr; p.a2 = g.A.ptr2; p.asc = g.A.sc; p.ash = g.A.sh; p.asc2 = g.A.sc2; p.a_amax = g.A.amax;
+    p.b = g.B.ptr; p.bsc = g.B.sc; p.bsh = g.B.sh;
+    p.b_scale = g.B.fscale != 0.f ? g.B.fscale : 1.f;
+    p.out = g.C;
+    p.status = g.status ? g.status : koaf_status_ptr();
+    p.M = g.M; p.N = g.N; p.K = g.K; p.splitk = g.splitk;
+    const dim3 grid((unsigned)((g.M / bm) * (g.N / bn)), (unsigned)g.splitk);
+    KoafGemm rec = g;
+    rec.bm = bm; rec.bn = bn;
+    koaf_log_launch("koaf_wgrad1", rec, grid, grid);
+    hipStream_t s = (hipStream_t)stream;
+    if (bm == 256 && bn == 256) return wg1_launch<256, 256>(p, g.A.tf, g.B.tf, grid, s);
+    if (bm == 256) return wg1_launch<256, 128>(p, g.A.tf, g.B.tf, grid, s);
+    return wg1_launch<128, 256>(p, g.A.tf, g.B.tf, grid, s);
+}

@@ -2,7 +2,8 @@
 (csrc/koaf_gemm*.hip, with the Makefile's own flags) with -Rpass-analysis=kernel-resource-usage (1 min) and prints VGPRs / spilled VGPRs / scratch per instantiation that spills, against the
 counts recorded when the round-4 regression was fixed (a 64-bit row index in the shared epilogue had cost every kernel ~30 VGPRs and
 the persistent 1x1 kernels 40-90 spilled registers: +40 ms per step, invisible in the build output).
-The one-pass optimizer / BCE kernels (koaf_optim.hip, koaf_bce.hip) are listed too and must not spill at all.
+The one-pass optimizer / BCE kernels (koaf_optim.hip, koaf_bce.hip) and the 256-wide-tile 1x1 weight-gradient kernels (koaf_wgrad1.hip)
+are listed too and must not spill at all.
     python scripts/check_spills.py"""
 import re, sys
 from pathlib import Path
@@ -17,8 +18,8 @@ RECORDED = {   # template arguments -> spilled VGPRs at the fixed build (koaf_ge
     "128,128,13,6,1,0,1,1,256,0,1,2": 22, "128,128,13,6,2,0,1,1,256,0,0,2": 0, "128,128,13,6,3,0,1,1,256,0,0,2": 0,
     "128,64,13,6,2,0,1,1,256,0,0,2": 0, "128,64,13,6,3,0,1,1,256,0,0,2": 0,
 }
-NO_SPILL_SRCS = ("koaf_optim.hip", "koaf_bce.hip")      # streams: every kernel of these files must report zero spills / scratch
-NO_SPILL = re.compile(r"(sgd|rmsprop|adam|adam_hyper|optim_hyper|bce(_sum)?)_kernel")
+NO_SPILL_SRCS = ("koaf_optim.hip", "koaf_bce.hip", "koaf_wgrad1.hip")      # streams: every kernel of these files must report zero spills / scratch
+NO_SPILL = re.compile(r"(sgd|rmsprop|adam|adam_hyper|optim_hyper|bce(_sum)?|wgrad1)_kernel")
 cmds = [c + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
         for src, c in compile_commands(CS) if src.startswith("koaf_gemm") or src in NO_SPILL_SRCS]
 txt = "".join(run_all(cmds, CS))
