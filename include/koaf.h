@@ -779,6 +779,40 @@ int koaf_pair_ranks(const void* a, int64_t stride_a, const void* b, int64_t stri
 int koaf_perm_metrics(const int32_t* packed, int32_t n, const uint32_t* masks, int32_t R, int32_t with_identity, double* out,
                       uint32_t* flag, void* stream);
 
+/* ---- from raw MRI series to the model's input volumes (koaf_mriprep.hip; run/prepare_data_mri_oai.py:185-189, :226, :234-279 and
+ * datasets/_mr_t2_mapping.py).  dtype: koaf_widen's codes and on: 2 = uint16, 3 = int16, 4 = float32, 5 = float64; every pointer
+ * is aligned to its element size, nothing more (a view into a larger buffer is read in place).  All fp64 arithmetic below is
+ * compiled without fused multiply-add and without reassociation; no floating-point atomics: the same bits from run to run.
+ *
+ * koaf_t2_fit  fit_t2_map: per voxel of vol [S][R][C][E] (echo fastest), with x = tes[s][e] (fp64 [S][E]) and y the intensity
+ *   widened to fp64 (int16 keeps its sign), the IEEE-754 evaluation of the reference's source text: the five sums S_x2_y += x*x*y,
+ *   S_y_lny += y*log(y), S_x_y += x*y, S_x_y_lny += x*y*log(y), S_y += y in echo order from 0.0; denom = S_y*S_x2_y - S_x_y*S_x_y;
+ *   a = (S_x2_y*S_y_lny - S_x_y*S_x_y_lny) / denom; b = (S_y*S_x_y_lny - S_x_y*S_y_lny) / denom; t = -1 / b.  In this order:
+ *   denom == 0, a NaN or b NaN -> 0;  t NaN -> nan_to;  t < val_low or t > val_high -> 0;  else t.  (A zero or negative intensity
+ *   makes y*log(y) NaN, so background becomes 0.  Only log differs from the host's, by its last bit.)  decimals >= 0: the value
+ *   stored is rint(v * 10^decimals) / 10^decimals, numpy's np.round, bit for bit; decimals < 0: v itself.  margin >= 0 voxels
+ *   are dropped at both ends of R and of C (2 * margin < R, C).  layout 0: out [S][R-2m][C-2m]; layout 1: out [R-2m][C-2m][S], the
+ *   reference's moveaxis(t2, [0,1,2], [2,0,1]).  2 <= E <= 16: with one echo denom is y*((x*x)*y) - (x*y)*(x*y), zero or one
+ *   ulp depending on rounding, and the reference's own answer is noise.  Series of several patients concatenate along S.
+ * koaf_series_hist  bins[u >> shift] += 1 over the n < 2^31 elements of x, u the uint16 that astype(np.uint16) makes of the
+ *   element (uint16 as is, int16 reinterpreted, floats truncated toward zero); bins is int32 [65536 >> shift], zeroed by the caller,
+ *   2 <= shift <= 8.  A float that is not finite raises bit 0 of *flag (a device word the caller zeroed), one outside [0, 65535]
+ *   bit 1; neither is counted.  Per-block counts in LDS, integer atomics only.
+ * koaf_series_quantiles  one block: out[j] = lerp(x_(k[j]), x_(min(k[j] + 1, n - 1)), gamma[j]) over the order statistics of the
+ *   counted values, numpy's _lerp: a + (b - a) * gamma, and b - (b - a) * (1 - gamma) where gamma >= 0.5.  k / gamma are HOST
+ *   arrays of K <= 8 pairs (they travel as kernel arguments), out fp64 [K] on the device; np.percentile(q) is k = floor(v),
+ *   gamma = v - k of v = (n - 1) * (q / 100) in fp64.  An index beyond the counted elements gives the largest counted value.
+ * koaf_series_pack  out[r - m][c - m][s] = narrow(min(max(u >> shift, limits[0]), limits[1])) of x [R][C][S]; limits is a DEVICE
+ *   fp64 pair (the two values koaf_series_quantiles left: no host round trip); the clip is np.clip's in fp64, narrow truncates
+ *   toward zero to uint8 (out16 = 0) or uint16 (out16 = 1).  margin m >= 1 (numpy's [0:-0] is empty), 2 m < R, C. */
+int koaf_t2_fit(const void* vol, int32_t dtype, const double* tes, int32_t S, int32_t R, int32_t C, int32_t E, double nan_to,
+                double val_low, double val_high, int32_t decimals, int32_t margin, int32_t layout, double* out, void* stream);
+int koaf_series_hist(const void* x, int32_t dtype, int64_t n, int32_t shift, int32_t* bins, uint32_t* flag, void* stream);
+int koaf_series_quantiles(const int32_t* bins, int32_t shift, int64_t n, const int64_t* k, const double* gamma, int32_t K,
+                          double* out, void* stream);
+int koaf_series_pack(const void* x, int32_t dtype, int32_t R, int32_t C, int32_t S, int32_t shift, int32_t margin,
+                     const double* limits, void* out, int32_t out16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
