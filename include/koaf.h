@@ -779,6 +779,56 @@ int koaf_pair_ranks(const void* a, int64_t stride_a, const void* b, int64_t stri
 int koaf_perm_metrics(const int32_t* packed, int32_t n, const uint32_t* masks, int32_t R, int32_t with_identity, double* out,
                       uint32_t* flag, void* stream);
 
+/* ---- the ROC / PR curves themselves, recall-range average precision, best calibrated F1 and confusion counts
+ * (koaf_metrics.hip; calc_metrics_v2(with_curves=True) of _metrics_stat_anlys.py:190-202, avg_precision_at_recall_range :11-25,
+ * mc_bacc :219-221, precision_recall_curve_calib / f1score_calib / bestf1score_calib of _metrics_wissam.py:113-231).  The same
+ * pieces as above -- `packed` of koaf_score_ranks, the histogram over the rank bins, the ordered walk -- with the walk's points
+ * written out, or folded into other scalars.  The arithmetic contract above holds unchanged: integer ranks, histograms and prefix
+ * sums; every fp64 value a quotient of such integers, one IEEE operation chain on them, or a sum of such chains in the fixed
+ * per-thread-run-then-tree order; no fused multiply-add, no floating-point atomics, the same bits from run to run.  n <=
+ * KOAF_METRICS_MAX_N; flag as above.
+ *
+ * koaf_curve_points  one block, the identity sample.  out is fp64 [koaf_curve_points_len(n)] = 8 + 8 * (n + 1): a length known
+ *   from n alone, so the points ride in the caller's one device-to-host copy.  With the T non-empty rank bins (sklearn's distinct
+ *   thresholds) in descending score order, tp / fp the running counts including the bin, P / N the totals:
+ *     out[0..8) = { P, N, T, K, last_ind, 0, 0, 0 }: K the number of thresholds roc_curve(drop_intermediate=True) keeps (the
+ *       first, the last, and every one whose (tp_g, fp_g) differs from the next threshold's), last_ind the index of the first
+ *       threshold with tp == P (tps.searchsorted(tps[-1]), where precision_recall_curve_calib truncates).
+ *     then eight arrays of n + 1 slots each:
+ *       0 thr       [j] = the score of threshold j, widened exactly                                            j in [0, T)
+ *       1 rec       [0] = 0,  [1 + j] = tp / P
+ *       2 prec      [0] = 1,  [1 + j] = tp / (tp + fp)
+ *       3 prec_cal  [0] = 1,  [1 + j] = tp / (tp + ratio * fp), 0 where that is NaN;  ratio = pi * (1 - pi0) / (pi0 * (1 - pi))
+ *                   in that order, pi = P / (P + N) -- or N / (P + N) when pi_of_negatives: the reference takes np.sum(y_true) / n,
+ *                   the share of LABEL 1, whichever class is called positive
+ *       4 fpr  5 tpr  6 roc thr   [0] = (0, 0, +inf),  [1 + k] = (fp / N, tp / P, score) of the k-th kept threshold   k in [0, K)
+ *       7 scratch (the score of each rank bin)
+ *     Slot 0 of arrays 1-3 is the closing point of the PR curves, so sklearn's precision_recall_curve is the reversed slice
+ *     [T .. 0] and the reference's calibrated curve the reversed slice [last_ind + 1 .. 0]: the host only slices and reverses.
+ *     Positions are counted (per-thread counts, an exclusive prefix over the 256 threads), never decided by an atomic.  Every
+ *     value is what numpy computes from the same integers, to the last bit.  Slots beyond T / K are not written.
+ * koaf_range_metrics  one block per row of out [rows][8] fp64; rows, idx, m and with_identity as for koaf_curve_metrics.  Along
+ *   the row's PR curve in ascending recall -- the leading (rec 0, prec 1) point, then the thresholds; bins empty in the resample
+ *   are no thresholds --
+ *     out[r] = { P, N, ap_range, best_f1_calib, rec_at_low, rec_at_high, 0, 0 }
+ *   rec_at_low = the largest rec <= lo, rec_at_high = the smallest rec >= hi (0 <= lo <= hi <= 1), ap_range = the sum of
+ *   (rec - rec_prev) * (prec + prec_prev) / 2.0 over the segments prev -> cur with rec > lo and rec_prev < hi (recall does not
+ *   decrease, so these are the segments between those two points; the comparisons are made on the quotients tp / P themselves),
+ *   divided by (rec_at_high - rec_at_low): scipy's trapezoid over sklearn's curve; 0 / 0 is NaN as on the host.
+ *   best_f1_calib = the maximum of (2 * p * r) / (p + r), NaN / Inf counting 0, over the points (p = prec_cal, r = rec) of the
+ *   calibrated curve up to the first threshold of full recall and its closing point (worth 0); pi = P / (P + N) of the row;
+ *   pi0 == 0 means pi0=None: no calibration, p = prec.  P == 0 or N == 0 writes the counts and NaN.
+ * koaf_confusion  counts[t * K + p] += 1 (int64 [K][K], zeroed by the caller) for each of the n < 2^31 samples with
+ *   t = y_true[i], p = y_pred[i] (int32 class indices), K <= 32: per-block LDS integer atomics, then global integer atomics.  A
+ *   label outside [0, K) raises flag bit 1 and the sample is skipped. */
+int64_t koaf_curve_points_len(int32_t n);
+int koaf_curve_points(const void* scores, int32_t f64, int64_t stride, const int32_t* packed, int32_t n, double pi0,
+                      int32_t pi_of_negatives, double* out, uint32_t* flag, void* stream);
+int koaf_range_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int32_t R, int32_t m, int32_t with_identity, double pi0,
+                       double lo, double hi, double* out, uint32_t* flag, void* stream);
+int koaf_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, int32_t K, int64_t* counts, uint32_t* flag,
+                   void* stream);
+
 /* ---- from raw MRI series to the model's input volumes (koaf_mriprep.hip; run/prepare_data_mri_oai.py:185-189, :226, :234-279 and
  * datasets/_mr_t2_mapping.py).  dtype: koaf_widen's codes and on: 2 = uint16, 3 = int16, 4 = float32, 5 = float64; every pointer
  * is aligned to its element size, nothing more (a view into a larger buffer is read in place).  All fp64 arithmetic below is

@@ -841,6 +841,102 @@ def point_metrics(scores, packed, thr=0.5, out=None, flag=None):
     return out
 
 
+def curve_points_len(n):
+    """the fp64 length of curve_points' buffer for n samples: 8 + 8 * (n + 1), known before anything is computed"""
+    return int(lib().koaf_curve_points_len(int(n)))
+
+
+def curve_points(scores, packed, pi0=0.12, pi_of_negatives=False, out=None, flag=None):
+    """The ROC / PR curve points of the sample itself in one fp64 buffer [curve_points_len(n)] (koaf_curve_points, one block): a
+    header (n_pos, n_neg, T thresholds, K kept ROC thresholds, last_ind, 0, 0, 0) and eight arrays of n + 1 slots -- thr, rec,
+    prec, prec calibrated to the prevalence pi0, roc fpr, roc tpr, roc thr, scratch; see koaf.h and parse_curve_points.
+    pi_of_negatives: the calibration takes the share of the NEGATIVES as the sample's prevalence (the reference's
+    np.sum(y_true) / n when class 0 is the positive one).  scores / packed / flag as in score_ranks."""
+    n, stride = _metric_scores("curve_points", scores)
+    _metric_i32("curve_points", "packed", packed, scores, (n,))
+    need = curve_points_len(n)
+    if out is None:
+        out = torch.empty(need, dtype=torch.float64, device=scores.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (need,) or out.device != scores.device:
+        raise KoafError(f"curve_points: out is contiguous fp64 [{need}] on the scores' device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(scores.device)
+    _metric_i32("curve_points", "flag", flag, scores, (1,))
+    check(lib().koaf_curve_points(_ptr(scores), 1 if scores.dtype == torch.float64 else 0, stride, _ptr(packed), n, float(pi0),
+                                  1 if pi_of_negatives else 0, _ptr(out), _ptr(flag), _stream()), "curve_points")
+    if own:
+        metrics_raise(flag.item())
+    return out
+
+
+def parse_curve_points(buf):
+    """the views into a HOST copy (numpy fp64) of curve_points' buffer: dict of n_pos, n_neg, T, K, last_ind and the arrays
+    thr [T]; rec / prec / prec_cal [T + 1] (slot 0 the closing (0, 1) point); fpr / tpr / roc_thr [K + 1] (slot 0 the leading
+    (0, 0, inf) point).  Slicing only: nothing is computed here."""
+    n = (buf.shape[0] - 8) // 8 - 1
+    P, N, T, K, last = (int(v) for v in buf[:5])
+    a = buf[8:].reshape(8, n + 1)
+    return {"n_pos": P, "n_neg": N, "T": T, "K": K, "last_ind": last, "thr": a[0, :T], "rec": a[1, :T + 1], "prec": a[2, :T + 1],
+            "prec_cal": a[3, :T + 1], "fpr": a[4, :K + 1], "tpr": a[5, :K + 1], "roc_thr": a[6, :K + 1]}
+
+
+def range_metrics(packed, idx=None, with_identity=True, pi0=0.12, recall_range=(0.0, 1.0), out=None, flag=None):
+    """out [rows, 8] fp64, row r = (n_pos, n_neg, average precision over the recall range, best calibrated F1, the recall at the
+    low end, at the high end, 0, 0) of one resample; rows / idx / with_identity / flag as in curve_metrics (koaf_range_metrics:
+    one block per row, fixed-order fp64 sums).  pi0 None: the F1 is not calibrated."""
+    if not torch.is_tensor(packed) or not packed.is_cuda:
+        raise KoafError("range_metrics: packed is the device tensor score_ranks returns")
+    _metric_i32("range_metrics", "packed", packed, packed)
+    n = int(packed.numel())
+    R = m = 0
+    if idx is not None:
+        _metric_i32("range_metrics", "idx", idx, packed)
+        if idx.dim() != 2 or idx.numel() == 0:
+            raise KoafError(f"range_metrics: idx is a non-empty [R, m] matrix, got {tuple(idx.shape)}")
+        R, m = int(idx.shape[0]), int(idx.shape[1])
+    rows = R + (1 if with_identity else 0)
+    if rows == 0:
+        raise KoafError("range_metrics: neither the identity row nor an index matrix")
+    if out is None:
+        out = torch.empty((rows, 8), dtype=torch.float64, device=packed.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (rows, 8) or out.device != packed.device:
+        raise KoafError(f"range_metrics: out is contiguous fp64 [{rows}, 8] on packed's device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(packed.device)
+    _metric_i32("range_metrics", "flag", flag, packed, (1,))
+    lo, hi = recall_range
+    check(lib().koaf_range_metrics(_ptr(packed), n, _ptr(idx), R, m, 1 if with_identity else 0, 0.0 if pi0 is None else float(pi0),
+                                   float(lo), float(hi), _ptr(out), _ptr(flag), _stream()), "range_metrics")
+    if own:
+        metrics_raise(flag.item())
+    return out
+
+
+def confusion(y_true, y_pred, K, out=None, flag=None):
+    """counts [K, K] int64, counts[t, p] = #{i : y_true[i] == t and y_pred[i] == p} of two int32 device vectors of class indices,
+    K <= 32 (koaf_confusion: integer atomics only).  out: a ZEROED int64 [K, K] to add into.  A label outside [0, K) is skipped and
+    raises flag bit 1 (flag as in score_ranks)."""
+    if not torch.is_tensor(y_true) or not y_true.is_cuda or y_true.dim() != 1 or y_true.numel() == 0:
+        raise KoafError("confusion: y_true is a non-empty 1-D int32 device vector")
+    _metric_i32("confusion", "y_true", y_true, y_true)
+    _metric_i32("confusion", "y_pred", y_pred, y_true, tuple(y_true.shape))
+    K = int(K)
+    if out is None:
+        out = torch.zeros((max(K, 0), max(K, 0)), dtype=torch.int64, device=y_true.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or tuple(out.shape) != (K, K) or out.device != y_true.device:
+        raise KoafError(f"confusion: out is contiguous int64 [{K}, {K}] on the labels' device, got {tuple(out.shape)} {out.dtype}")
+    own = flag is None
+    if own:
+        flag = metrics_flag(y_true.device)
+    _metric_i32("confusion", "flag", flag, y_true, (1,))
+    check(lib().koaf_confusion(_ptr(y_true), _ptr(y_pred), int(y_true.numel()), K, _ptr(out), _ptr(flag), _stream()), "confusion")
+    if own:
+        metrics_raise(flag.item())
+    return out
+
+
 def pair_ranks(scores_a, scores_b, labels=None, pos_label=1, flag=None):
     """score_ranks over the UNION of two score columns of the same n samples (koaf_pair_ranks): element j < n is scores_a[j],
     element n + j is scores_b[j]; rank[j] = #{k : union[k] > union[j]} (int32 [2n]), so equal scores of the two models share a
