@@ -318,18 +318,26 @@ static inline bool wgrad3_ring_shape(int N, int H, int W, int Cin, int Cout, int
     return KH == 3 && KW == 3 && stride == 1 && pad == 1 && koaf_wgrad3_ring_ok(N, H, W, Cin, Cout);
 }
 
-// koaf_wgrad1.hip: 1x1 / stride 1 over the fp32 tensors on 256-wide tiles, same split-K plan and slabs
+// koaf_wgrad1.hip: 1x1 / stride 1, and stride 2 (1x1 / pad 0, 3x3 / pad 1), over the fp32 tensors on 256-wide tiles, same split-K plan and slabs
 int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream);
 // the tile on which koaf_wgrad1 takes the weight gradient described by g under plan p (bm = 0: the generic kernel keeps it): the fp16
 // scheme on fp32 tensors, channel counts in whole tiles of 128 with at least one side 256 wide, and k-ranges of at least WGRAD1_MIN_KCHUNK
-// pixels -- shorter launches stay with the generic kernel's more and smaller blocks
+// pixels -- shorter launches stay with the generic kernel's more and smaller blocks.  B is dense (1x1 / stride 1) or the stride-2 gather
+// of a 1x1 / pad 0 or 3x3 / pad 1 filter whose Cin is a whole number of column tiles (a block then works on one filter tap); layer2's
+// 3x3 / stride 2 at 128 -> 128 (N = 1152: no whole number of 256-wide tiles beside M = 128) and every other gather stay on koaf_gemm
 constexpr int WGRAD1_MIN_KCHUNK = 1024;
-static inline WgradPlan wgrad1_tile(const KoafGemm& g, const WgradPlan& p, bool pointwise) {
+static inline WgradPlan wgrad1_tile(const KoafGemm& g, const WgradPlan& p) {
     WgradPlan t = {0, 0, p.splitk};
-    if (!pointwise || g.fmt != 1 || g.act16 != 0 || g.A.kind != 1 || g.B.kind != 1) return t;
+    const KoafOperand& B = g.B;
+    if (g.fmt != 1 || g.act16 != 0 || g.A.kind != 1 || B.kind != 1 || g.A.gather || (B.gather != 0 && B.gather != 1)) return t;
     if (g.M % 128 || g.N % 128 || (g.M < 256 && g.N < 256)) return t;
     const int bm = g.M >= 256 ? 256 : 128, bn = g.N >= 256 ? 256 : 128;
     if (g.M % bm || g.N % bn) return t;
+    if (B.gather == 1) {
+        const bool f11 = B.KH == 1 && B.KW == 1 && B.pad == 0 && B.pad_w == 0, f33 = B.KH == 3 && B.KW == 3 && B.pad == 1 && B.pad_w == 1;
+        if (B.stride != 2 || !(f11 || f33) || B.CS != B.C || B.C % bn || B.PH <= 0 || B.PW <= 0) return t;
+        if ((int64_t)(g.K / (B.PH * B.PW)) * B.H * B.W >= (1ll << 31)) return t;      // (the kernel's table holds 31-bit pixel indices)
+    }
     if (rup32(cdiv64(g.K, p.splitk)) < WGRAD1_MIN_KCHUNK) return t;
     // (what koaf_gemm's vector path asks of the pointers; an unaligned call takes the generic kernel's scalar path)
     if (!aligned16(g.A.ptr) || !aligned16(g.B.ptr) || !aligned16(g.C)) return t;
@@ -396,7 +404,7 @@ extern "C" int koaf_conv2d_wgrad(const float* dy, const float* x, float* dw, int
     g.C = p.splitk > 1 ? slabs : dw;
     g.ldc = Ntot;
     g.act16 = (act16 && !dy_planes) ? 3 : 0;      // (x and dy_apply->c are bf16 activations; plane images carry no storage type)
-    const WgradPlan t1 = wgrad1_tile(g, p, is_pointwise(KH, KW, stride, pad));
+    const WgradPlan t1 = wgrad1_tile(g, p);
     int rc = t1.bm ? koaf_wgrad1(g, t1.bm, t1.bn, stream) : koaf_gemm(&g, stream);
     if (rc != KOAF_OK || p.splitk == 1) return rc;
     return koaf_slab_reduce(slabs, p.splitk, (int64_t)Cout * Ntot, dw, stream);

@@ -1,5 +1,6 @@
-// koaf_wgrad1.hip -- weight gradient of the 1x1 / stride-1 convolutions on 256-wide tiles (k = pixel):
-//     dw[co][ci] = sum_p dc[p][co] * x~[p][ci]
+// koaf_wgrad1.hip -- weight gradient of the 1x1 / stride-1 convolutions, and of the stride-2 ones (1x1 shortcuts, 3x3 / pad 1), on
+// 256-wide tiles (k = pixel):
+//     dw[co][ci] = sum_p dc[p][co] * x~[p][ci]                  (stride 2: dw[co][tap][ci], x~ at the tap's source pixel of p, 0 outside)
 // with both operands K-major fp32 in HBM and the transforms of koaf_gemm's loaders formed on load: dc = dy, or the BatchNorm-backward
 // apply k0 dz + k3 - k2 c of two sources (KoafOperand.tf 2); x~ = x, or relu(in_sc x + in_sh) (tf 1).  fp16 scheme only
 // (KoafGemm.fmt 1: two fp16 pieces per value, three MFMAs per product).
@@ -17,6 +18,12 @@
 // Arithmetic, pieces, LDS images (plane[k][ROWS + 32 pad], koaf_pieces.h) and the order of the piece products per accumulator and
 // 16-k slice are those of TileLoader + koaf_gemm_kernel's mma(): slabs and dw are bit-identical to the generic path
 // (tests/test_wgrad1x1_gpu.py).  Split-K plan, slab layout and the XCD remap are koaf_gemm's.
+// Stride 2 (GB = true): B is x gathered on the k index as TileLoader<.., M_KM_G1> gathers it.  Cin is a whole number of column tiles,
+// so a block works on ONE filter tap (kh, kw).  The source pixel of a k-row costs no persistent register: the first 32 lanes of wave 0
+// compute, three k-steps ahead, the 32 pixel indices of a k-tile (the divisions: once per k-step and block) into a ring of four table
+// rows in LDS; a loader thread reads its unit's entry when it issues the unit and keeps one validity bit per unit until it converts it.
+// A row that is padding or lies behind the k-range loads pixel 0 and is zeroed behind the transform, as finish_unit does; the zero
+// contributions enter the accumulators where the generic kernel's do (tests/test_wgrad1_gather_gpu.py: torch.equal).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -38,12 +45,18 @@ struct Wg1Params {
     float* out;            // slabs [splitk][M][N], or dw [M][N] when splitk == 1
     uint32_t* status;
     int M, N, K, splitk;
+    // gathered B (stride 2): x is [n][H][W][C] (pixel stride C), k = (n, oy, ox) of the PH x PW output grid, column = (tap, ci)
+    int H, W, C, PH, PW, KW, stride, pad, pad_w;
 };
 
 constexpr int WG1_NT = 512;
 
+constexpr int WG1_TAB = 4 * BK;          // gathered B: ring of four table rows (k-tiles s + 1 .. s + 3 are live during step s)
+constexpr unsigned WG1_INVALID = 0x80000000u;
+
 // one K-major fp32 operand of the block: R columns of the 32 rows of a k-tile, 4 columns x (R / 64) rows ("units") per thread
-template <int R, int TF>
+// G: the rows are gathered through the block's table of source pixels (issue_g); ld is then the pixel stride of the source
+template <int R, int TF, bool G = false>
 struct Wg1Loader {
     static constexpr int NU = R / 64;                 // units per thread and k-tile
     static constexpr int CV = R / 4;                  // threads across a k-row
@@ -57,6 +70,7 @@ struct Wg1Loader {
     const float* src2;
     float fsc;
     unsigned ld, col, kr;
+    unsigned vm;           // G: bit i = unit i holds a row that is padding or lies behind the k-range
 
     __device__ __forceinline__ void init(const float* p, const float* p2, const float* sc, const float* sh, const float* sc2,
                                          int c0, int ldim, float scale) {
@@ -66,6 +80,7 @@ struct Wg1Loader {
         ld = (unsigned)ldim;
         col = (unsigned)c0 + 4u * (t % CV);
         kr = t / CV;
+        vm = 0u;
         ca = cb = ck = (v4f){0.f, 0.f, 0.f, 0.f};
         if constexpr (TF != 0) {
             ca = *(const v4f*)(sc + col) * fsc;
@@ -83,12 +98,19 @@ struct Wg1Loader {
         r[i] = *(const v4f*)(src + base + off);
         if constexpr (TF == 2) r2[i] = *(const v4f*)(src2 + base + off);
     }
+    // G: loads of unit i of the k-tile whose table row is T -- entry = source pixel index, or WG1_INVALID (the load then re-reads pixel 0)
+    __device__ __forceinline__ void issue_g(int i, const unsigned* T) {
+        const unsigned e = T[kr + (unsigned)(RP * i)];
+        vm = (vm & ~(1u << i)) | ((e >> 31) << i);
+        const uint64_t off = (uint64_t)(e & ~WG1_INVALID) * ld + col;  // (N H W C reaches 3 G elements)
+        r[i] = *(const v4f*)(src + off);
+    }
     // TileLoader::finish_unit's arithmetic + split2h + the store of TileLoader::store, for unit i of the k-tile whose klim first
-    // rows lie inside the k-range
+    // rows lie inside the k-range (G: validity is the unit's bit, border taps included; there is no FULL form)
     template <bool FULL>
     __device__ __forceinline__ void convert(int i, int klim, unsigned* S) {
         constexpr float HMAX = 65504.f;
-        const bool ok = FULL || (int)(kr + (unsigned)(RP * i)) < klim;
+        const bool ok = G ? ((vm >> i) & 1u) == 0u : (FULL || (int)(kr + (unsigned)(RP * i)) < klim);
         v4f v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -112,15 +134,16 @@ struct Wg1Loader {
     }
 };
 
-template <int BM, int BN, int TFA, int TFB>
+template <int BM, int BN, int TFA, int TFB, bool GB>
 __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
     constexpr int WGM = 4, WGN = 2;                                   // waves along M x N
     constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 32, TN = WN / 32;
     typedef Wg1Loader<BM, TFA> LA;
-    typedef Wg1Loader<BN, TFB> LB;
+    typedef Wg1Loader<BN, TFB, GB> LB;
     constexpr int A_ELEMS = 2 * LA::PL, B_ELEMS = 2 * LB::PL, STAGE = A_ELEMS + B_ELEMS;
-    static_assert(2 * STAGE * 4 <= 160 * 1024, "two stages of both operands in LDS");
-    __shared__ __attribute__((aligned(16))) unsigned smem[2 * STAGE];
+    static_assert((2 * STAGE + WG1_TAB) * 4 <= 160 * 1024, "two stages of both operands in LDS");
+    __shared__ __attribute__((aligned(16))) unsigned smem[2 * STAGE + (GB ? WG1_TAB : 0)];
+    [[maybe_unused]] unsigned* const tab = smem + 2 * STAGE;
 
     // block -> (k-range, tile): koaf_gemm_kernel's split-K remap -- XCD = linear id % 8 takes the splits = x (mod 8), all tiles of a
     // split in consecutive slots of one XCD (one L2)
@@ -149,7 +172,23 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
     LA la;
     LB lb;
     la.init(p.a, p.a2, p.asc, p.ash, p.asc2, m0, p.M, sca);
-    lb.init(p.b, nullptr, p.bsc, p.bsh, nullptr, n0, p.N, scb);
+    // gathered B: the block's filter tap and its first channel (C % BN == 0); table row j & 3 holds the source pixels of k-tile j
+    [[maybe_unused]] int g_kh = 0, g_kw = 0;
+    if constexpr (GB) {
+        const int tap = n0 / p.C;
+        g_kh = tap / p.KW;
+        g_kw = tap - g_kh * p.KW;
+        lb.init(p.b, nullptr, p.bsc, p.bsh, nullptr, n0 - tap * p.C, p.C, scb);
+    } else
+        lb.init(p.b, nullptr, p.bsc, p.bsh, nullptr, n0, p.N, scb);
+    [[maybe_unused]] auto table = [&](int j, int lane32) {
+        const int k = kbeg + j * BK + lane32;
+        const unsigned kk = (unsigned)min(k, p.K - 1), ppi = (unsigned)(p.PH * p.PW);
+        const unsigned n = kk / ppi, rem = kk - n * ppi, oy = rem / (unsigned)p.PW, ox = rem - oy * (unsigned)p.PW;
+        const int sy = (int)oy * p.stride - p.pad + g_kh, sx = (int)ox * p.stride - p.pad_w + g_kw;
+        const bool ok = k < kend && (unsigned)sy < (unsigned)p.H && (unsigned)sx < (unsigned)p.W;
+        tab[(j & 3) * BK + lane32] = ok ? (n * (unsigned)p.H + (unsigned)sy) * (unsigned)p.W + (unsigned)sx : WG1_INVALID;
+    };
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int wm = w / WGN, wn = w % WGN;
@@ -171,7 +210,8 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             la.issue(u, k2, p.K);
         } else {
             lb.template convert<FULL>(u - LA::NU, klim, S + A_ELEMS);
-            lb.issue(u - LA::NU, k2, p.K);
+            if constexpr (GB) lb.issue_g(u - LA::NU, tab + (((k2 - kbeg) / BK) & 3) * BK);
+            else lb.issue(u - LA::NU, k2, p.K);
         }
     };
     // k-step: the MFMAs of the stage at cur -- per accumulator the order of koaf_gemm_kernel's mma(): 16-k slice g, then lo*hi, hi*lo,
@@ -180,6 +220,10 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
         const unsigned* Au = smem + cur * STAGE;
         const unsigned* Bu = Au + A_ELEMS;
         unsigned* Sn = smem + (cur ^ 1) * STAGE;
+        if constexpr (GB) {
+            // the table row of the k-tile after k2: its readers pass this step's barrier first; the row it replaces was last read three steps ago
+            if (threadIdx.x < BK) table((k2 - kbeg) / BK + 1, threadIdx.x);
+        }
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             v4i ap[TM][2];
@@ -213,10 +257,17 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
     };
 
     if (nstep > 0) {
+        if constexpr (GB) {
+            if (threadIdx.x < 3 * BK) table(threadIdx.x / BK, threadIdx.x % BK);
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
 #pragma unroll
         for (int i = 0; i < LA::NU; ++i) la.issue(i, kbeg, p.K);
 #pragma unroll
-        for (int i = 0; i < LB::NU; ++i) lb.issue(i, kbeg, p.K);
+        for (int i = 0; i < LB::NU; ++i) {
+            if constexpr (GB) lb.issue_g(i, tab);
+            else lb.issue(i, kbeg, p.K);
+        }
 #pragma unroll
         for (int u = 0; u < NUT; ++u) unit(std::false_type{}, u, klen, smem, kbeg + BK);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -247,39 +298,54 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             }
 }
 
-template <int BM, int BN>
+template <int BM, int BN, bool GB>
 int wg1_launch(const Wg1Params& p, int tfa, int tfb, dim3 grid, hipStream_t s) {
-#define WG1_GO(TA, TB) hipLaunchKernelGGL((wgrad1_kernel<BM, BN, TA, TB>), grid, dim3(WG1_NT), 0, s, p)
+#define WG1_GO(TA, TB) hipLaunchKernelGGL((wgrad1_kernel<BM, BN, TA, TB, GB>), grid, dim3(WG1_NT), 0, s, p)
     if (tfa == 2) { if (tfb) WG1_GO(2, 1); else WG1_GO(2, 0); }
     else { if (tfb) WG1_GO(0, 1); else WG1_GO(0, 0); }
 #undef WG1_GO
     return koaf_check_launch("koaf_wgrad1");
 }
+template <bool GB>
+int wg1_tile(const Wg1Params& p, int bm, int bn, int tfa, int tfb, dim3 grid, hipStream_t s) {
+    if (bm == 256 && bn == 256) return wg1_launch<256, 256, GB>(p, tfa, tfb, grid, s);
+    if (bm == 256) return wg1_launch<256, 128, GB>(p, tfa, tfb, grid, s);
+    return wg1_launch<128, 256, GB>(p, tfa, tfb, grid, s);
+}
 }  // namespace
 
 void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
 
-// the 1x1 / stride-1 weight gradient described by g (koaf_conv2d_wgrad's descriptor: A = dy [K][M] K-major with tf 0 | 2, B = x [K][N]
-// K-major with tf 0 | 1, fmt 1, act16 0, C = slabs or dw) on bm x bn tiles; the caller has checked the dispatch rule (koaf_conv.hip wgrad1_tile)
+// the weight gradient described by g (koaf_conv2d_wgrad's descriptor: A = dy [K][M] K-major with tf 0 | 2, B = x with tf 0 | 1 -- [K][N]
+// K-major for 1x1 / stride 1, or gather 1 over the NHWC tensor for stride 2 --, fmt 1, act16 0, C = slabs or dw) on bm x bn tiles; the
+// caller has checked the dispatch rule (koaf_conv.hip wgrad1_tile)
 int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream) {
-    KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && g.A.kind == 1 && g.B.kind == 1 && !g.A.gather && !g.B.gather && g.A.amax && g.A.ptr && g.B.ptr &&
-                 g.C && (g.A.tf == 0 || (g.A.tf == 2 && g.A.ptr2 && g.A.sc && g.A.sh && g.A.sc2)) && (g.B.tf == 0 || (g.B.tf == 1 && g.B.sc && g.B.sh)) &&
+    const KoafOperand& B = g.B;
+    const bool gb = B.gather == 1;
+    KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && g.A.kind == 1 && B.kind == 1 && !g.A.gather && (B.gather == 0 || gb) && g.A.amax && g.A.ptr && B.ptr &&
+                 g.C && (g.A.tf == 0 || (g.A.tf == 2 && g.A.ptr2 && g.A.sc && g.A.sh && g.A.sc2)) && (B.tf == 0 || (B.tf == 1 && B.sc && B.sh)) &&
                  (bm == 256 || bm == 128) && (bn == 256 || bn == 128) && bm + bn >= 384 && g.M % bm == 0 && g.N % bn == 0 && g.K >= BK && g.K < (1 << 30) &&
-                 g.splitk >= 1 && g.splitk <= 65535 && g.A.ld == g.M && g.B.ld == g.N && g.ldc == g.N,
+                 g.splitk >= 1 && g.splitk <= 65535 && g.A.ld == g.M && (gb || B.ld == g.N) && g.ldc == g.N,
                  "koaf_wgrad1: bad args");
+    // the gathered form: stride 2, a 1x1 / pad 0 or 3x3 / pad 1 filter, the whole pixel is the tap's channels, a column tile inside one tap,
+    // k = whole images of the output grid, and a source pixel index that fits the table's 31 bits
+    KOAF_REQUIRE(!gb || (B.stride == 2 && B.KH == B.KW && B.pad == B.pad_w && ((B.KH == 1 && B.pad == 0) || (B.KH == 3 && B.pad == 1)) &&
+                         (B.CS == 0 || B.CS == B.C) && B.C % bn == 0 && g.N == B.KH * B.KW * B.C && B.PH > 0 && B.PW > 0 &&
+                         B.PH == (B.H + 2 * B.pad - B.KH) / 2 + 1 && B.PW == (B.W + 2 * B.pad_w - B.KW) / 2 + 1 && g.K % (B.PH * B.PW) == 0 &&
+                         (int64_t)(g.K / (B.PH * B.PW)) * B.H * B.W < (1ll << 31)),
+                 "koaf_wgrad1: bad gather");
     Wg1Params p;
     p.a = g.A.ptr; p.a2 = g.A.ptr2; p.asc = g.A.sc; p.ash = g.A.sh; p.asc2 = g.A.sc2; p.a_amax = g.A.amax;
-    p.b = g.B.ptr; p.bsc = g.B.sc; p.bsh = g.B.sh;
-    p.b_scale = g.B.fscale != 0.f ? g.B.fscale : 1.f;
+    p.b = B.ptr; p.bsc = B.sc; p.bsh = B.sh;
+    p.b_scale = B.fscale != 0.f ? B.fscale : 1.f;
     p.out = g.C;
     p.status = g.status ? g.status : koaf_status_ptr();
     p.M = g.M; p.N = g.N; p.K = g.K; p.splitk = g.splitk;
+    p.H = B.H; p.W = B.W; p.C = B.C; p.PH = B.PH; p.PW = B.PW; p.KW = B.KW; p.stride = B.stride; p.pad = B.pad; p.pad_w = B.pad_w;
     const dim3 grid((unsigned)((g.M / bm) * (g.N / bn)), (unsigned)g.splitk);
     KoafGemm rec = g;
     rec.bm = bm; rec.bn = bn;
     koaf_log_launch("koaf_wgrad1", rec, grid, grid);
     hipStream_t s = (hipStream_t)stream;
-    if (bm == 256 && bn == 256) return wg1_launch<256, 256>(p, g.A.tf, g.B.tf, grid, s);
-    if (bm == 256) return wg1_launch<256, 128>(p, g.A.tf, g.B.tf, grid, s);
-    return wg1_launch<128, 256>(p, g.A.tf, g.B.tf, grid, s);
+    return gb ? wg1_tile<true>(p, bm, bn, g.A.tf, B.tf, grid, s) : wg1_tile<false>(p, bm, bn, g.A.tf, B.tf, grid, s);
 }
