@@ -504,6 +504,32 @@ int koaf_minmax(const float* x, int32_t B, int64_t n, float* mm, float* ws, void
 int koaf_augment(const float* x, float* y, const float* mm, const float* params, int32_t B, int32_t R, int32_t C,
                  int32_t S, float mean, float stdv, void* stream);
 
+/* ---- the same pipeline from the STORED volumes (koaf_inpipe.hip): np.flip of RIGHT knees (datasets/oai/_dataset.py:298-321),
+ * RandomCrop | CenterCrop (preproc/_np_nd.py:62-144), NumpyToTensor, the four transforms above and PTInterpolate(0.5, 0.5[, 0.5 |
+ * 1.0]) (run/train_prog_fus.py:111-116) without a cropped, flipped or widened copy.  Every sample is read in place through a
+ * DEVICE table of 8 x int64 per sample:
+ *   [0] address of stored voxel (0, 0, 0)        [1..3] stored extents R0, C0, S0 (contiguous, S fastest; a radiograph: S0 = 1)
+ *   [4..6] origin r0, c0, s0: the stored index of window voxel 0 on each axis
+ *   [7] bit mask of the axes walked backwards (1 = R, 2 = C, 4 = S): window index i is stored index origin - i there, + i elsewhere
+ * The window R x C x S (S = 1: radiographs) is the same for the whole batch; stored extents and origins are per sample, so ragged
+ * volumes need no stacking.  dtype of the stored elements: 0 = fp32, 1 / 2 / 3 = uint8 / uint16 / int16 as in koaf_widen; the
+ * address is aligned to the element, nothing more.  The caller checks every window against its volume before the table is
+ * uploaded (ops.window_rows refuses such a row on the host, so the Python layer never reaches what follows).  As a defence only, for
+ * a caller of this ABI that did not, the kernels re-read the row's extents and do not dereference a row whose window leaves them:
+ * its (min, max) and its output are NaN.  The extents themselves and the address are taken on trust.
+ * koaf_window_minmax  mm [B][2] = (min, max) over the window only, exact (integers below 2^24 convert exactly); two stages in a
+ *   fixed order, no atomics; ws: B * koaf_window_minmax_ws(R * C * S) floats.
+ * koaf_input_pipeline  y = mean over pool x pool x pool_s window voxels of f, pool and pool_s in {1, 2} dividing R, C and S:
+ *   f = koaf_augment's arithmetic at window coordinates with mm and params [B][4] as there; a bilinear neighbour outside the
+ *   WINDOW reads as zero whatever the stored volume holds there (the reference rotates the cropped tensor).  The pool is
+ *   koaf_downscale2's sum in its order times 1 / (pool * pool * pool_s).  layout 0: y [B][R/pool][C/pool][S/pool_s], the
+ *   reference's; 1: y [B][S/pool_s][R/pool][C/pool], slice-major.  A constant window divides 0 by 0: NaN, as the reference. */
+int64_t koaf_window_minmax_ws(int64_t n);
+int koaf_window_minmax(const int64_t* table, int32_t dtype, int32_t B, int32_t R, int32_t C, int32_t S, float* mm, float* ws,
+                       void* stream);
+int koaf_input_pipeline(const int64_t* table, int32_t dtype, float* y, const float* mm, const float* params, int32_t B, int32_t R,
+                        int32_t C, int32_t S, int32_t pool, int32_t pool_s, int32_t layout, float mean, float stdv, void* stream);
+
 /* ---- MaxPool2d 3x3 s2 p1 over relu(sc*c+sh) (_torchvision.py:173-174), GAP (:182) ------------ */
 int koaf_maxpool_fwd(const float* c, const float* sc, const float* sh, float* y, uint8_t* argmax,
                      int32_t N, int32_t H, int32_t W, int32_t C, int32_t act16, void* stream);
