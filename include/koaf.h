@@ -855,6 +855,39 @@ int koaf_range_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int
 int koaf_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, int32_t K, int64_t* counts, uint32_t* flag,
                    void* stream);
 
+/* ---- the clinical logistic-regression baseline (koaf_clin.hip; run/train_prog_clin.py with scikit-learn's StandardScaler,
+ * OneHotEncoder and LogisticRegression(lbfgs, L2, fit_intercept) behind it).  Everything is fp64.  Every sum has one owner and a
+ * fixed order and there are no floating-point atomics: the same bits from run to run.  *flag is a device word the caller zeroed;
+ * bit 0: a NaN / Inf in the table, in a weight, or a fit that left the finite range; bit 1: a category that is not in the list;
+ * bit 2: a problem whose weighted rows hold one class; bit 3: a label other than 0 / 1 under a non-zero weight, a negative
+ * weight, or a fitting-row index outside [0, n).
+ *
+ * koaf_clin_design  raw [V][n] holds one column per variable; ncat (HOST, [V]) is 0 for a continuous variable and the number of
+ *   categories otherwise; cats (HOST) holds the strictly increasing categories of the categorical variables one after another
+ *   (np.unique of the fitting rows).  fit = 1: stats[v] = (mean, population standard deviation) of every continuous variable over
+ *   the rows fit_idx[0 .. nfit) (device int32; NULL: all rows, nfit = n) is computed first (two passes, ddof = 0) and left in
+ *   stats [V][2]; fit = 0: stats is read.  X [n][D] row-major: (x - mean) / std for a continuous variable (std 0 divides by 1),
+ *   one 0 / 1 column per category in list order otherwise, the variables in the caller's order; D + 1 <= KOAF_LOGREG_MAX_P.
+ * koaf_logreg_fit  K problems over the same X [n][D] and y [n] (int32 0 / 1), problem k with the weights sw[k][0 .. n): a weight
+ *   of 0 takes the row out of the problem (its X values enter no sum, whatever they are), so fold masks and class weights are one mechanism.
+ *   Minimises  f(w) = (1/S) sum_i s_i [log(1 + e^{r_i}) - y_i r_i] + |w[:D]|^2 / (2 C S),  r_i = x_i . w[:D] + w[D],  S = sum_i s_i,
+ *   by Newton steps (Cholesky of the exact Hessian) damped by Armijo backtracking t = 1, 1/2, ...:  f(w + t d) <= f(w) +
+ *   1e-4 t g.d + 4 eps |f(w)|.  It stops at |g|_inf <= tol, when no t >= 2^-30 passes, or after max_iter steps.  One block per
+ *   problem, all K in one launch.  W [K][D + 1], the intercept last; report [K][4] = (steps taken, final |g|_inf, final f, step
+ *   halvings).  A problem whose weights or labels raise a bit (0, 2 or 3) leaves NaN in its rows of W and report.  2 <= n, D + 1 <= KOAF_LOGREG_MAX_P.
+ * koaf_logreg_predict  decision [K][m] = Xt [m][D] . W[k][:D] + W[k][D], proba [K][m][2] = (1 - p, p) with p = 1 / (1 + e^-decision).
+ *   logloss != NULL: logloss[k] = -mean over the rows with mask[k][i] != 0 (int32 [K][m]) of log(clip(p of class y[i], eps,
+ *   1 - eps)), sklearn.metrics.log_loss; NaN without such a row.  ensemble = 1: ens_proba [m][2] = the mean over the K problems
+ *   (added in problem order, then divided) and ens_pred [m] its argmax, the first index winning a tie. */
+#define KOAF_LOGREG_MAX_P 32
+int koaf_clin_design(const double* raw, int64_t n, int32_t V, const int32_t* ncat, const double* cats, const int32_t* fit_idx,
+                     int64_t nfit, int32_t fit, double* stats, double* X, uint32_t* flag, void* stream);
+int koaf_logreg_fit(const double* X, const int32_t* y, const double* sw, int64_t n, int32_t D, int32_t K, double C, int32_t max_iter,
+                    double tol, double* W, double* report, uint32_t* flag, void* stream);
+int koaf_logreg_predict(const double* W, const double* Xt, int64_t m, int32_t D, int32_t K, const int32_t* y, const int32_t* mask,
+                        int32_t ensemble, double* decision, double* proba, double* logloss, double* ens_proba, int32_t* ens_pred,
+                        void* stream);
+
 /* ---- from raw MRI series to the model's input volumes (koaf_mriprep.hip; run/prepare_data_mri_oai.py:185-189, :226, :234-279 and
  * datasets/_mr_t2_mapping.py).  dtype: koaf_widen's codes and on: 2 = uint16, 3 = int16, 4 = float32, 5 = float64; every pointer
  * is aligned to its element size, nothing more (a view into a larger buffer is read in place).  All fp64 arithmetic below is

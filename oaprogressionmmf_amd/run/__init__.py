@@ -1,5 +1,5 @@
 """Step bodies and regimes of the reference's drivers (koafusion/run/train_prog_fus.py, eval_prog_fus.py) on the MI355X
-path: train, validation (with its metrics table, various.calc_metrics_v2), evaluation and explanation.  The drivers' shell
+path: train, validation (with its metrics table, various.calc_metrics_v2), evaluation and explanation, and the logistic-regression baselines of train_prog_clin.py.  The drivers' shell
 (hydra, data loaders, tensorboard, fit()'s checkpoint bookkeeping) stays the reference's."""
 from ._steps import downscale_inputs, train_epoch, train_step, predict_batch, val_epoch
 from ._eval import eval_epoch, ensemble_eval_foldw, InferenceTimer
@@ -9,8 +9,10 @@ from ._explain import (explain_epoch, ensemble_explain_foldw, modal_ablation, ab
                        saliency_maps)
 from ._gradcam import GradCam, cam_strides, gradcam
 from ._attr import attribution_totals, integrated_gradients, quadrature, smoothgrad
+from ._clin import clin_design, clin_fit, clin_vars
 
 __all__ = ["downscale_inputs", "train_epoch", "train_step", "predict_batch", "val_epoch", "eval_epoch", "ensemble_eval_foldw",
            "InferenceTimer", "GraphedPredictor", "GraphedTrainStep", "explain_epoch", "ensemble_explain_foldw", "modal_ablation",
            "ablation_percent", "input_gradients", "saliency_maps", "GradientFold", "micro_batch_weights", "train_step_accum", "GradCam",
-           "cam_strides", "gradcam", "attribution_totals", "integrated_gradients", "quadrature", "smoothgrad"]
+           "cam_strides", "gradcam", "attribution_totals", "integrated_gradients", "quadrature", "smoothgrad", "clin_design", "clin_fit",
+           "clin_vars"]
