@@ -1,0 +1,99 @@
+"""Explanations: class-activation maps (koaf_cam.hip) and the path attributions -- integrated gradients, SmoothGrad
+(koaf_attr.hip)."""
+import torch
+
+from .._lib import KoafError, check, defines, lib
+from ._base import _a16, _ptr, _stream
+
+
+def cam(A, w, N, HW, C, relu=True):
+    """cam[n][p] = sum_c A[n][p][c] * w[n][c] (clamped at 0 with `relu`) of an NHWC feature map A (fp32 or bf16 storage) and fp32
+    weights w [N, C] -> (cam [N, HW], img_sum [N] = sum_p cam, img_max [N] = max_p |cam|), all fp32 (koaf_cam: fixed order)"""
+    if A.dtype not in (torch.float32, torch.bfloat16) or w.dtype != torch.float32:
+        raise KoafError(f"cam: an fp32 / bf16 feature map and fp32 weights, got {A.dtype} and {w.dtype}")
+    if not (A.is_contiguous() and w.is_contiguous()) or A.numel() != N * HW * C or w.numel() != N * C:
+        raise KoafError(f"cam: contiguous A [{N}, {HW}, {C}] and w [{N}, {C}], got {tuple(A.shape)} and {tuple(w.shape)}")
+    out = torch.empty((N, HW), device=A.device, dtype=torch.float32)
+    stat = torch.empty((2, N), device=A.device, dtype=torch.float32)
+    check(lib().koaf_cam(_ptr(A), _ptr(w), _ptr(out), _ptr(stat[0]), _ptr(stat[1]), N, HW, C, 1 if relu else 0, _a16(A), _stream()),
+          "cam")
+    return out, stat[0], stat[1]
+
+
+CAM_NORMALIZE = {None: 0, "sample": 1, "image": 2}
+
+
+def cam_upsample(cam, img_max, out, B, K, h, w, H, W, strides, normalize=None):
+    """image b*K + k of cam [B*K, h, w] resized to H x W (bilinear, align_corners=False), divided by a maximum (normalize: None,
+    "sample" = the largest img_max of the sample's K images, "image" = its own) and written to out[b*sb + k*sk + i*si + j*sj],
+    strides = (sb, sk, si, sj) in elements (koaf_cam_upsample: one write pass).  Elements of `out` no (b, k, i, j) reaches stay."""
+    if normalize not in CAM_NORMALIZE:
+        raise ValueError(f"Unknown normalize: {normalize}")
+    if cam.dtype != torch.float32 or out.dtype != torch.float32 or not (cam.is_contiguous() and out.is_contiguous()):
+        raise KoafError("cam_upsample: contiguous fp32 tensors only")
+    if cam.numel() != B * K * h * w or (img_max is not None and (img_max.numel() != B * K or not img_max.is_contiguous())):
+        raise KoafError(f"cam_upsample: cam [{B * K}, {h}, {w}] and img_max [{B * K}], got {tuple(cam.shape)}")
+    sb, sk, si, sj = (int(s) for s in strides)
+    if min(sb, sk, si, sj) <= 0 or (B - 1) * sb + (K - 1) * sk + (H - 1) * si + (W - 1) * sj >= out.numel():
+        raise KoafError(f"cam_upsample: strides {(sb, sk, si, sj)} leave the {out.numel()} elements of out")
+    check(lib().koaf_cam_upsample(_ptr(cam), _ptr(img_max), _ptr(out), B, K, h, w, H, W, sb, sk, si, sj, CAM_NORMALIZE[normalize],
+                                  _stream()), "cam_upsample")
+    return out
+
+
+ATTR_MAX_J = defines()["KOAF_ATTR_MAX_J"]
+
+
+def _attr_rows(what, x, base):
+    """(B, n) of a contiguous fp32 (B, ...) tensor x; base: None, a python number or a tensor like x -> (tensor | None, value)"""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 1 or x.numel() == 0:
+        raise KoafError(f"{what}: a contiguous, non-empty fp32 tensor (B, ...), got "
+                        f"{(tuple(x.shape), x.dtype) if torch.is_tensor(x) else type(x)}")
+    if torch.is_tensor(base):
+        if base.dtype != torch.float32 or not base.is_contiguous() or tuple(base.shape) != tuple(x.shape) or base.device != x.device:
+            raise KoafError(f"{what}: a baseline tensor is contiguous fp32 of x's shape {tuple(x.shape)} on x's device, got "
+                            f"{tuple(base.shape)} {base.dtype} on {base.device}")
+        return int(x.shape[0]), x.numel() // int(x.shape[0]), base, 0.0
+    return int(x.shape[0]), x.numel() // int(x.shape[0]), None, 0.0 if base is None else float(base)
+
+
+def _attr_coefs(what, c, like):
+    """the J alphas / weights: a device fp32 vector [J], 1 <= J <= KOAF_ATTR_MAX_J"""
+    if not torch.is_tensor(c) or c.dtype != torch.float32 or c.dim() != 1 or not c.is_contiguous() or c.device != like.device:
+        raise KoafError(f"{what}: the coefficients are a contiguous fp32 vector on the tensors' device")
+    if not 1 <= c.numel() <= ATTR_MAX_J:
+        raise KoafError(f"{what}: 1 <= J <= {ATTR_MAX_J}, got J = {c.numel()}")
+    return int(c.numel())
+
+
+def path_points(x, alpha, base=None, mm=None, noise_level=0.0, seed=0, draw0=0):
+    """out[j] = base + alpha[j] * (x - base) + sigma_b * z(seed, draw0 + j, b, i) -> [J, *x.shape] (koaf_path_points: x and base
+    read once for all J; no fused operation).  base: None (zeros), a python number, or a tensor like x.  alpha: device fp32 [J].
+    mm: the [B, 2] of ops.minmax(x, B), sigma_b = noise_level * (max_b - min_b); mm None or noise_level 0 draws nothing."""
+    B, n, bt, bv = _attr_rows("path_points", x, base)
+    J = _attr_coefs("path_points", alpha, x)
+    if mm is not None and (mm.dtype != torch.float32 or not mm.is_contiguous() or tuple(mm.shape) != (B, 2) or mm.device != x.device):
+        raise KoafError(f"path_points: mm is the contiguous fp32 [{B}, 2] of ops.minmax, got {tuple(mm.shape)} {mm.dtype}")
+    if not (0 <= int(draw0) and int(draw0) + J <= 2 ** 31):
+        raise KoafError(f"path_points: draw indices lie in [0, 2^31), got draw0 = {draw0}")
+    out = torch.empty((J,) + tuple(x.shape), device=x.device, dtype=torch.float32)
+    check(lib().koaf_path_points(_ptr(x), _ptr(bt), bv, _ptr(alpha), _ptr(out), J, B, n, _ptr(mm), float(noise_level),
+                                 int(seed) & (2 ** 64 - 1), int(draw0), _stream()), "path_points")
+    return out
+
+
+def attr_fold(acc, g, w, square=False, first=False, x=None, base=None):
+    """acc (=|+=) sum_j w[j] * f(g[j]) in index order, f the identity or (square) the square; g [J, *acc.shape], w device fp32
+    [J]; first: write instead of accumulate.  With x given (the last chunk of an integrated-gradients path) the stored value is
+    additionally multiplied by (x - base), base as in path_points (koaf_attr_fold: one pass, no fused operation).  Returns acc."""
+    B, n, bt, bv = _attr_rows("attr_fold", acc, base if x is not None else None)
+    J = _attr_coefs("attr_fold", w, acc)
+    if not torch.is_tensor(g) or g.dtype != torch.float32 or not g.is_contiguous() or tuple(g.shape) != (J,) + tuple(acc.shape) \
+            or g.device != acc.device:
+        raise KoafError(f"attr_fold: g is contiguous fp32 [{J}, *{tuple(acc.shape)}] on acc's device, got "
+                        f"{(tuple(g.shape), g.dtype) if torch.is_tensor(g) else type(g)}")
+    if x is not None and (x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != tuple(acc.shape) or x.device != acc.device):
+        raise KoafError(f"attr_fold: x is contiguous fp32 of acc's shape {tuple(acc.shape)}, got {tuple(x.shape)} {x.dtype}")
+    check(lib().koaf_attr_fold(_ptr(acc), _ptr(g), _ptr(w), _ptr(x), _ptr(bt), bv, J, B, n, 1 if square else 0, 1 if first else 0,
+                               1 if x is not None else 0, _stream()), "attr_fold")
+    return acc
