@@ -1059,6 +1059,13 @@ __global__ void __launch_bounds__(NT, (persist_mode(AM, BMD, F16, TFA) || AM == 
         const int scol = n0 + wn * WN + 32 * jn + r;
         kshift[jn] = (do_stats && p.stats_shift && scol < p.N) ? p.stats_shift[(int64_t)blockIdx.z * p.stats_bs + scol] : 0.f;
     }
+    // Rows of a ragged last tile past M were accumulated as zeros.  Under a shift each puts (0 - k) and k^2 into the sums above;
+    // taking n k and n k^2 out again afterwards leaves the rounding of sums as large as n k^2 in a tile whose own rows may sum to
+    // far less (4 real rows of 128: 3.5e-5 of the sum of squares, 3e-4 of the sum).  Such a tile sums its real rows from the
+    // staged tile instead.  Block-uniform; full tiles and unshifted statistics run what they always ran.
+    const int mreal = p.M - m0;                  // real rows of this tile (>= BM: all of them)
+    const bool ragged_shift = do_stats && p.stats_shift != nullptr && mreal < BM;
+    [[maybe_unused]] float rg1 = 0.f, rg2 = 0.f;
 
     if constexpr (VEC) {
         // stage the accumulator tile through LDS so global stores (and residual / bias loads) are
@@ -1189,6 +1196,18 @@ __global__ void __launch_bounds__(NT, (persist_mode(AM, BMD, F16, TFA) || AM == 
             }
         }
         if (do_stats) __syncthreads();           // Cs is about to be reused by the statistics reduction
+        if (ragged_shift) {
+            // the staged tile still holds every accumulator: this column's sums over the tile's real rows only
+            if (t < BN && (n0 + t) < p.N) {
+                const float k = p.stats_shift[(int64_t)blockIdx.z * p.stats_bs + n0 + t];
+                for (int row = 0; row < mreal; ++row) {
+                    const float d = Cs[row * LDC_S + t] - k;
+                    rg1 += d;
+                    rg2 = fmaf(d, d, rg2);
+                }
+            }
+            __syncthreads();
+        }
     } else {
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -1201,8 +1220,9 @@ __global__ void __launch_bounds__(NT, (persist_mode(AM, BMD, F16, TFA) || AM == 
             for (int e = 0; e < 16; ++e) {
                 const int row = m0 + wm * WM + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * h;
                 float v = alpha * acc[i][jn][e];
-                s1[i][jn] += v - kshift[jn];
-                s2[i][jn] = fmaf(v - kshift[jn], v - kshift[jn], s2[i][jn]);     // (explicit: every instantiation rounds alike)
+                const float k = row < p.M ? kshift[jn] : 0.f;       // (rows past M hold zeros: summed about 0, they add nothing)
+                s1[i][jn] += v - k;
+                s2[i][jn] = fmaf(v - k, v - k, s2[i][jn]);     // (explicit: every instantiation rounds alike)
                 if (cok && row < p.M) {
                     v += bv;
                     if (Rp) v += Rp[(int64_t)row * p.ldr + col];
@@ -1253,12 +1273,8 @@ __global__ void __launch_bounds__(NT, (persist_mode(AM, BMD, F16, TFA) || AM == 
 #pragma unroll
                 for (int m = 1; m < WGM; ++m) { a1 += red[(2 * m) * BN + t]; a2 += red[(2 * m + 1) * BN + t]; }
             }
-            if (p.stats_shift) {
-                // rows of the tile past M were accumulated as zeros: each put (0 - k) and k^2 into the shifted sums
-                const float k = p.stats_shift[(int64_t)blockIdx.z * p.stats_bs + n0 + t];
-                const int ninv = max(0, m0 + BM - p.M);
-                a1 += (float)ninv * k;
-                a2 -= (float)ninv * k * k;
+            if constexpr (VEC) {
+                if (ragged_shift) { a1 = rg1; a2 = rg2; }
             }
             st[n0 + t] = a1;
             st[p.stats_ld + n0 + t] = a2;

@@ -163,6 +163,7 @@ def test_gconv3x3(dev, C, groups, stride, H, scheme):
     assert rel_err(nchw(y.cpu()), y_ref) < 2e-6
     yr = y_ref.detach().permute(1, 0, 2, 3).reshape(C, -1)
     assert rel_err(part[:, 0].double().sum(0).cpu(), yr.sum(1)) < 1e-4
+    assert rel_err(part[:, 1].double().sum(0).cpu(), (yr * yr).sum(1)) < 1e-5
     dyd = nhwc(dy).to(dev)
     if scheme == "f16":
         dyd._koaf_amax = dyd.abs().max().reshape(1)
