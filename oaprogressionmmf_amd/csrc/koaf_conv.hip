@@ -116,6 +116,24 @@ __global__ void __launch_bounds__(256) gconv_compress_kernel(const float* __rest
 // ================================================================================================
 // dense convolution
 // ================================================================================================
+// koaf_fwd_s2.hip: the stride-2 forward convolutions (1x1 / pad 0, 3x3 / pad 1) over the fp32 tensors on 256-row tiles, bit-identical to
+// koaf_gemm_kernel on the same descriptor
+int koaf_fwd_s2(const KoafGemm& g, void* stream);
+// does koaf_fwd_s2 take the forward convolution described by g?  The fp16 scheme with the F plane image, fp32 tensors at pixel stride Cin,
+// no plane-image input, tail or emission, whole k-tiles inside a tap (Cin % 32 == 0), whole column tiles (Cout % 128 == 0), whole 256-row
+// tiles (M % 256 == 0: a ragged last tile stays with the generic kernel, and so do the 128-row tiles its small calls are tested on),
+// 16-B aligned pointers, a source pixel index that fits 31 bits and, behind a prologue, no more channels than the kernel's coefficient
+// table holds (1024).  One k-tile is the shortest K the pipeline is written for.
+static inline bool fwd_s2_ok(const KoafGemm& g, int KH, int KW, int stride, int pad, bool x_planes, bool tail, bool emit) {
+    const KoafOperand& A = g.A;
+    if (stride != 2 || KH != KW || !((KH == 1 && pad == 0) || (KH == 3 && pad == 1))) return false;
+    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || g.act16 != 0 || x_planes || tail || emit) return false;
+    if (A.kind != 0 || A.gather != 1 || A.amax || (A.C % 32) != 0 || A.CS != A.C || (g.N % 128) != 0 || (g.M % 256) != 0 || g.K < 32) return false;
+    if (A.tf != 0 && (A.tf != 1 || A.C > 1024 || !aligned16(A.sc) || !aligned16(A.sh))) return false;
+    if (!aligned16(A.ptr) || !aligned16(g.B.planes) || !aligned16(g.C)) return false;
+    return (int64_t)(g.M / (A.PH * A.PW)) * A.H * A.W < (1ll << 31);
+}
+
 extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t N, int32_t H, int32_t W, int32_t Cin,
                                int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* in_sc,
                                const float* in_sh, float* stats, int32_t* stats_rows, const float* stats_shift,
@@ -157,6 +175,10 @@ extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t
     if (emit) {
         KOAF_REQUIRE(emit->planes && emit->sc && emit->sh && (Cout % 8) == 0, "koaf_conv2d_fwd: emit needs planes / sc / sh and Cout %% 8 == 0");
         g.out_planes = emit->planes; g.out_sc = emit->sc; g.out_sh = emit->sh; g.out_ps = M * Cout;
+    }
+    if (fwd_s2_ok(g, KH, KW, stride, pad, x_planes != nullptr, tail != nullptr, emit != nullptr)) {
+        if (stats_rows) *stats_rows = g.M / 128;        // two partial rows per 256-row tile: the rows of a 128-row tiling
+        return koaf_fwd_s2(g, stream);
     }
     if (stats_rows) *stats_rows = koaf_gemm_part_rows(&g);
     return koaf_gemm(&g, stream);
