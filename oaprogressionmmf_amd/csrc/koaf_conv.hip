@@ -215,6 +215,30 @@ extern "C" int32_t koaf_conv2d_dgrad_bnb_rows(int32_t N, int32_t H, int32_t W, i
     return (int32_t)cdiv64((int64_t)N * H * W, 64);
 }
 
+// koaf_dgrad_s2.hip: one parity class of a stride-2 data gradient (3x3 / pad 1 over dy's plane images; class (0, 0) of a 1x1 / pad 0
+// shortcut over the fp32 tensors, with the zeros of the three classes without a tap) on 256-row tiles, bit-identical to koaf_gemm_kernel
+// on the same class descriptors
+int koaf_dgrad_s2(const KoafGemm& g, void* stream);
+// does koaf_dgrad_s2 take the class described by g (and with it the whole call: the rule reads nothing that differs between the classes
+// that have a tap)?  The fp16 scheme with the D plane image on fp32 tensors, no residual, no fused reduction or mode 2 with one
+// BatchNorm; 3x3 / pad 1 from dy's plane images (reduction optional), 1x1 / pad 0 from the fp32 dy (tf 0 | 2) without a reduction; whole
+// k-tiles inside a tap (Cout % 32 == 0), whole column tiles (Cin % 128 == 0); an even image whose classes are whole 256-row tiles (a ragged
+// tile or an odd image stays with the generic kernel, and so do the 128-row tiles its small calls are tested on); 16-B aligned pointers.
+// (Pixel indices fit 31 bits: koaf_conv2d_dgrad_bnb requires N H W < 2^31.)
+static inline bool dgrad_s2_ok(const KoafGemm& g, int KH, int KW, int pad, int H, int W, const KoafBnb* bnb, bool dy_planes) {
+    const KoafOperand& A = g.A;
+    const bool f11 = KH == 1 && KW == 1 && pad == 0, f33 = KH == 3 && KW == 3 && pad == 1;
+    if (!(f11 || f33) || (H & 1) || (W & 1) || (g.M % 256) != 0 || g.K < 32) return false;
+    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || !A.amax || g.act16 != 0 || g.residual) return false;
+    if ((A.C % 32) != 0 || (g.N % 128) != 0 || !aligned16(g.C) || !aligned16(g.B.planes)) return false;
+    if (bnb && (bnb->mode != 2 || bnb->c2 || !aligned16(bnb->c) || !aligned16(bnb->sc) || !aligned16(bnb->sh) || !aligned16(bnb->mean) ||
+                !aligned16(bnb->invstd) || !aligned16(g.bnb_part)))
+        return false;
+    if (f33) return dy_planes && A.kind == 2 && aligned16(A.planes) && aligned16(A.zeros) && !(A.plane_stride & 7);
+    if (dy_planes || bnb || A.kind != 0 || !aligned16(A.ptr)) return false;
+    return A.tf == 0 || (A.tf == 2 && aligned16(A.ptr2) && aligned16(A.sc) && aligned16(A.sh) && aligned16(A.sc2));
+}
+
 extern "C" int koaf_conv2d_dgrad_bnb(const float* dy, const float* w, float* dx, int32_t N, int32_t H, int32_t W,
                                      int32_t Cin, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad,
                                      const float* residual, const KoafBnb* bnb, float* part, int32_t* part_rows,
@@ -248,8 +272,10 @@ extern "C" int koaf_conv2d_dgrad_bnb(const float* dy, const float* w, float* dx,
         // classes (y%2, x%2) are four stride-1 transposed gathers over their own tap subsets -- 4x less MFMA work
         // than multiplying the structural zeros of the plain gather.  Each class scatters its rows straight from
         // the epilogue (row map); a class with no tap (1x1 kernels) just writes residual / zero.
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
+        // (koaf_dgrad_s2 on class (0, 0) of a 1x1 shortcut also writes the three classes without a tap: all_done)
+        bool all_done = false;
+        for (int py = 0; py < 2 && !all_done; ++py)
+            for (int px = 0; px < 2 && !all_done; ++px) {
                 const int Hc = (H - py + 1) / 2, Wc = (W - px + 1) / 2;
                 if (Hc <= 0 || Wc <= 0) continue;
                 const int khs = (py + pad) & 1, kws = (px + pad) & 1;
@@ -274,11 +300,16 @@ extern "C" int koaf_conv2d_dgrad_bnb(const float* dy, const float* w, float* dx,
                 g.C = dx; g.ldc = Cin;
                 g.residual = residual; g.ldr = Cin;
                 g.cmap = 1; g.cm_PH = Hc; g.cm_PW = Wc; g.cm_H = H; g.cm_W = W; g.cm_py = py; g.cm_px = px;
-                if (bnb) {
-                    set_bnb(&g, bnb, part + (int64_t)rows_done * nsum * Cin);
-                    rows_done += koaf_gemm_part_rows(&g);
-                }
                 g.act16 = act16 ? 2 : 0;
+                if (bnb) set_bnb(&g, bnb, part + (int64_t)rows_done * nsum * Cin);
+                if (dgrad_s2_ok(g, KH, KW, pad, H, W, bnb, dy_planes != nullptr)) {
+                    if (bnb) rows_done += g.M / 128;        // two partial rows per 256-row tile: the rows of a 128-row tiling
+                    int rc = koaf_dgrad_s2(g, stream);
+                    if (rc != KOAF_OK) return rc;
+                    all_done = KH == 1;
+                    continue;
+                }
+                if (bnb) rows_done += koaf_gemm_part_rows(&g);
                 int rc = koaf_gemm(&g, stream);
                 if (rc != KOAF_OK) return rc;
             }
