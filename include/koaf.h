@@ -584,6 +584,30 @@ int koaf_path_points(const float* x, const float* base, float base_value, const 
 int koaf_attr_fold(float* acc, const float* g, const float* w, const float* x, const float* base, float base_value, int32_t J,
                    int32_t B, int64_t n, int32_t square, int32_t first, int32_t finish, void* stream);
 
+/* ---- Attention relevance of the FeaT fusion: rollout and the gradient-weighted rule (koaf_attnrel.hip; not in the reference) ----
+ * All tensors are contiguous fp32, any n, h, d >= 1 (tiles are guarded, nothing needs a multiple).  Full fp32 products; sums in a
+ * fixed order in fp32 or fp64; no atomics: run-to-run identical bits.  Outputs may not overlap inputs (refused).
+ *
+ * koaf_attn_layer  the per-layer matrix abar [B][n][n] from koaf_attention_fwd's attn [B][h][n][n].
+ *   mode 0 | 1 | 2 (rollout, Abnar & Zuidema 2020): f[i][j] = mean | max | min over heads of attn (heads in index order; the mean
+ *   is the running sum divided by h), + 1 at j == i; abar[i][j] = f[i][j] / sum_j f[i][j], the row sum formed in fp64 and the
+ *   quotient rounded once.  dout and qkv are NULL.  At most h + 2 roundings per element, all terms >= 0.
+ *   mode 3 (Chefer et al. 2021, self-attention rule): abar[i][j] = (1 / h) sum_h relu(attn[h][i][j] * dP[h][i][j]),
+ *   dP[h][i][j] = sum_k dout[i][h d + k] * qkv[j][2 h_all d + h d + k]  (dout [B][n][h d]: the gradient with respect to the
+ *   attention core's output; qkv [B][n][3 h d]: the fused projection in the '(qkv h d)' split, whose third part is V) -- one fmaf
+ *   chain over k in index order per element, held in registers: dP is never stored.  Heads are added in index order and the sum
+ *   is divided by h.  A NaN in a product stays.  B <= 65535.
+ * koaf_attn_apply  r_out[b][qi][j] = sum_m r_in[b][qi][m] * abar[b][m][j]  (+ r_in[b][qi][j] when add_identity): a few relevance
+ *   rows carried through one layer from the left.  r_in [B][q][n], or NULL for the identity (q == n: r_out = abar, + I when
+ *   add_identity, exactly).  The m range is cut into sixteen interleaved fmaf chains added as a pairwise tree.  B <= 65535.
+ * koaf_attn_segsum  out[b][k] = sum_{u < t} r[b][off + k t + u], k in [0, K): per-slice (t tokens a slice) and per-modality
+ *   (K = 1) totals of a relevance row r [B][n]; off + K t <= n.  Terms in index order into an fp64 sum, rounded once. */
+int koaf_attn_layer(const float* attn, const float* dout, const float* qkv, float* abar, int32_t B, int32_t n, int32_t h, int32_t d,
+                    int32_t mode, void* stream);
+int koaf_attn_apply(const float* r_in, const float* abar, float* r_out, int32_t B, int32_t q, int32_t n, int32_t add_identity,
+                    void* stream);
+int koaf_attn_segsum(const float* r, float* out, int32_t B, int32_t n, int32_t off, int32_t K, int32_t t, void* stream);
+
 /* ---- Input plumbing -------------------------------------------------------------------------- */
 /* "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209-210): x [B,R,C,S] -> out [B*S,R,C] */
 int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,

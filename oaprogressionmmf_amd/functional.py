@@ -156,6 +156,27 @@ class AttentionFn(torch.autograd.Function):
         return dqkv, None, None
 
 
+class AttnTape(object):
+    """What run.attention_relevance needs of every attention call, in call order: the Attention module it ran in, the fused
+    projection, the attention tensor, (B, n, heads, d), the stream it ran on (the per-MRI aggregators run on their encoder's lane)
+    and -- once a backward has passed -- the gradient with respect to the attention core's output.  Installed as
+    `functional.ATTN_TAPE` for one call; while that is None (always, otherwise) nothing is recorded and nothing is kept."""
+
+    def __init__(self):
+        self.calls = []
+
+    def record(self, module, qkv, out, attn, heads):
+        B, n, three_dim = qkv.shape
+        rec = {"module": module, "qkv": qkv.detach(), "attn": attn.detach(), "dims": (B, n, heads, three_dim // (3 * heads)),
+               "dout": None, "stream": torch.cuda.current_stream()}
+        if out.requires_grad:
+            out.register_hook(lambda g: rec.__setitem__("dout", g.detach()))
+        self.calls.append(rec)
+
+
+ATTN_TAPE = None       # an AttnTape while run.attention_relevance runs its forward (and backward)
+
+
 class GeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -1,4 +1,6 @@
 """Pieces shared by the six registry models."""
+from typing import NamedTuple, Optional, Tuple
+
 import torch
 from torch import nn
 
@@ -134,6 +136,59 @@ def maybe_restore(model, config, path_weights):
     apply_activation_storage(model, config)
     if config["restore_weights"]:
         model.load_state_dict(torch.load(path_weights, map_location="cpu"))
+
+
+class TokenSegment(NamedTuple):
+    """the tokens of one model input in the final FeaT's sequence: `offset` counts from behind the CLS tokens; `per_slice`
+    tokens make one slice (a radiograph or the clinical vector is one slice: per_slice == length); `agg`: the input's own
+    aggregator FeaT (no CLS token: its state s is final token offset + s), or None where the tokens enter the final FeaT directly"""
+    input: int
+    offset: int
+    length: int
+    per_slice: int
+    agg: Optional[nn.Module]
+
+
+class TokenLayout(NamedTuple):
+    segments: Tuple[TokenSegment, ...]
+    ncls: int
+    feat: nn.Module
+
+
+def token_layout(model):
+    """Which tokens of the final FeaT belong to which input: (segments in sequence order, number of CLS tokens, the final FeaT),
+    from the class's `vs` dict and the concatenation order its forward uses.  A model without a FeaT raises a ValueError."""
+    from ._ext import _HierFusionC1
+    from ._mrN_cnn_trf import MR1CnnTrf, MR2CnnTrf
+    from ._xr1mrN import XR1MR1CnnTrf, XR1MR2CnnTrf
+    from ._xrNmrMcP import XR1MR2C1CnnTrf
+    import math
+    vs = getattr(model, "vs", None)
+    parts = []                                  # (input, length, tokens per slice or None, aggregator or None)
+    if isinstance(model, MR1CnnTrf):
+        sp = vs["fe_out_spat"]
+        per = {"rc": sp[0] * sp[1], "cs": sp[1] * sp[2], "rs": sp[0] * sp[2]}[model.config["fe"]["dims_view"]]
+        feat, parts = model._agg, [(0, vs["agg_in_len"], per, None)]
+    elif isinstance(model, MR2CnnTrf):
+        per, ns = math.prod(vs["fe_out_spat"]), model.config["agg"]["num_slices"]
+        feat, parts = model._agg, [(0, ns[0] * per, per, None), (1, ns[1] * per, per, None)]
+    elif isinstance(model, XR1MR1CnnTrf):
+        feat = model._agg
+        parts = [(0, vs["agg_in_len_0"], None, None), (1, vs["agg_in_len_1"], math.prod(vs["fe1_out_spat"]), None)]
+    elif isinstance(model, (XR1MR2CnnTrf, XR1MR2C1CnnTrf, _HierFusionC1)):
+        # [radiographs | every MRI's aggregator states | clinical]: the inputs in their order
+        feat, i = model._agg_final, 0
+        while f"agg_in_len_{i}" in vs:
+            agg = getattr(model, f"_agg_{i}", None)
+            parts.append((i, vs[f"agg_in_len_{i}"], math.prod(vs[f"fe{i}_out_spat"]) if agg is not None else None, agg))
+            i += 1
+    else:
+        raise ValueError(f"{type(model).__name__} has no FeaT: there is no attention to read a relevance from")
+    segs, off = [], 0
+    for i, length, per, agg in parts:
+        segs.append(TokenSegment(i, off, int(length), int(per if per is not None else length), agg))
+        off += int(length)
+    return TokenLayout(tuple(segs), int(feat.cls_token.shape[1]) if feat.with_cls else 0, feat)
 
 
 MAPPING_CH = {"resnet18": 512, "resnet34": 512, "resnet50": 2048, "resnext50_32x4d": 2048}

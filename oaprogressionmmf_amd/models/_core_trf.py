@@ -81,6 +81,8 @@ class Attention(nn.Module):
             raise NotImplementedError("the reference's mask path is dead code (_core_trf.py:2,173 raises); mask must be None")
         qkv = KF.linear(x, self.to_qkv.weight, None)
         out, attn = KF.attention(qkv, self.heads, self.scale)
+        if KF.ATTN_TAPE is not None:
+            KF.ATTN_TAPE.record(self, qkv, out, attn, self.heads)
         lo, p = self.to_out[0], self.to_out[1].p
         if residual is not None and not (self.training and p > 0):
             return KF.linear(out, lo.weight, lo.bias, residual=residual), attn

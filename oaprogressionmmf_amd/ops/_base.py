@@ -108,7 +108,7 @@ def conv_out(h, k, s, p):
 # ------------------------------------------------------------------------------------------------
 # argument checks of the wrappers that take caller-made buffers (metrics, mriprep, clin)
 # ------------------------------------------------------------------------------------------------
-_DTYPE_NAME = {torch.int32: "int32", torch.int64: "int64", torch.float64: "fp64"}
+_DTYPE_NAME = {torch.int32: "int32", torch.int64: "int64", torch.float64: "fp64", torch.float32: "fp32"}
 
 
 def check_tensor(what, name, t, dtype, shape=None, like=None, nonempty=False, where="the HIP device"):

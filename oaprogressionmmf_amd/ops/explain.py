@@ -1,9 +1,9 @@
-"""Explanations: class-activation maps (koaf_cam.hip) and the path attributions -- integrated gradients, SmoothGrad
-(koaf_attr.hip)."""
+"""Explanations: class-activation maps (koaf_cam.hip), the path attributions -- integrated gradients, SmoothGrad
+(koaf_attr.hip) -- and the attention relevance of the fusion transformers (koaf_attnrel.hip)."""
 import torch
 
 from .._lib import KoafError, check, defines, lib
-from ._base import _a16, _ptr, _stream
+from ._base import _a16, _ptr, _stream, check_tensor, out_buffer
 
 
 def cam(A, w, N, HW, C, relu=True):
@@ -97,3 +97,74 @@ def attr_fold(acc, g, w, square=False, first=False, x=None, base=None):
     check(lib().koaf_attr_fold(_ptr(acc), _ptr(g), _ptr(w), _ptr(x), _ptr(bt), bv, J, B, n, 1 if square else 0, 1 if first else 0,
                                1 if x is not None else 0, _stream()), "attr_fold")
     return acc
+
+
+# ------------------------------------------------------------------------------------------------
+# attention relevance of the FeaT fusion (koaf_attnrel.hip)
+# ------------------------------------------------------------------------------------------------
+ATTN_MODES = ("mean", "max", "min", "grad")
+
+
+def attn_layer(attn, mode, dout=None, qkv=None, out=None):
+    """the per-layer matrix abar [B, n, n] of an attention tensor attn [B, h, n, n] (koaf_attn_layer).  mode "mean" | "max" | "min":
+    attention rollout -- the heads fused, the identity added, rows divided by their sum.  mode "grad": mean_h relu(dP * attn) with
+    dP = dout_i . V_j, from dout [B, n, h*d] (the gradient with respect to the attention core's output) and the fused projection
+    qkv [B, n, 3*h*d]; dP is never stored."""
+    if mode not in ATTN_MODES:
+        raise ValueError(f"Unknown attention mode: {mode}")
+    check_tensor("attn_layer", "attn", attn, torch.float32, nonempty=True)
+    if attn.dim() != 4 or attn.shape[2] != attn.shape[3]:
+        raise KoafError(f"attn_layer: attn is [B, h, n, n], got {tuple(attn.shape)}")
+    B, h, n, _ = (int(s) for s in attn.shape)
+    d = 1
+    if mode == "grad":
+        if dout is None or qkv is None:
+            raise KoafError("attn_layer: mode grad needs dout [B, n, h*d] and qkv [B, n, 3*h*d]")
+        check_tensor("attn_layer", "dout", dout, torch.float32, like=attn, nonempty=True, where="attn's device")
+        if dout.dim() != 3 or tuple(dout.shape[:2]) != (B, n) or dout.shape[2] % h:
+            raise KoafError(f"attn_layer: dout is [{B}, {n}, {h} * d], got {tuple(dout.shape)}")
+        d = int(dout.shape[2]) // h
+        check_tensor("attn_layer", "qkv", qkv, torch.float32, (B, n, 3 * h * d), attn, where="attn's device")
+    elif dout is not None or qkv is not None:
+        raise KoafError(f"attn_layer: mode {mode} takes no dout / qkv")
+    out = out_buffer("attn_layer", out, (B, n, n), torch.float32, attn, "attn's device")
+    check(lib().koaf_attn_layer(_ptr(attn), _ptr(dout), _ptr(qkv), _ptr(out), B, n, h, d, ATTN_MODES.index(mode), _stream()),
+          "attn_layer")
+    return out
+
+
+def attn_apply(abar, r_in=None, add_identity=False, out=None):
+    """r_out [B, q, n] = r_in [B, q, n] . abar [B, n, n] (+ r_in with add_identity): relevance rows carried through one layer from
+    the left (koaf_attn_apply).  r_in None: the identity, q = n.  `out` may alias neither input."""
+    check_tensor("attn_apply", "abar", abar, torch.float32, nonempty=True)
+    if abar.dim() != 3 or abar.shape[1] != abar.shape[2]:
+        raise KoafError(f"attn_apply: abar is [B, n, n], got {tuple(abar.shape)}")
+    B, n, _ = (int(s) for s in abar.shape)
+    q = n
+    if r_in is not None:
+        check_tensor("attn_apply", "r_in", r_in, torch.float32, like=abar, nonempty=True, where="abar's device")
+        if r_in.dim() != 3 or r_in.shape[0] != B or r_in.shape[2] != n:
+            raise KoafError(f"attn_apply: r_in is [{B}, q, {n}], got {tuple(r_in.shape)}")
+        q = int(r_in.shape[1])
+    out = out_buffer("attn_apply", out, (B, q, n), torch.float32, abar, "abar's device")
+    for name, t in (("abar", abar), ("r_in", r_in)):
+        if t is not None and out.numel() and t.numel() and out.data_ptr() < t.data_ptr() + 4 * t.numel() \
+                and t.data_ptr() < out.data_ptr() + 4 * out.numel():
+            raise KoafError(f"attn_apply: out aliases {name}")
+    check(lib().koaf_attn_apply(_ptr(r_in), _ptr(abar), _ptr(out), B, q, n, 1 if add_identity else 0, _stream()), "attn_apply")
+    return out
+
+
+def attn_segsum(r, off, K, t, out=None):
+    """out [B, K]: out[b, k] = sum of r[b, off + k*t : off + (k+1)*t] for a relevance row r [B, n] -- per-slice totals (t tokens a
+    slice) or, with K = 1, a modality's total (koaf_attn_segsum: index order, one rounding)."""
+    check_tensor("attn_segsum", "r", r, torch.float32, nonempty=True)
+    if r.dim() != 2:
+        raise KoafError(f"attn_segsum: r is [B, n], got {tuple(r.shape)}")
+    B, n = (int(s) for s in r.shape)
+    off, K, t = int(off), int(K), int(t)
+    if off < 0 or K < 1 or t < 1 or off + K * t > n:
+        raise KoafError(f"attn_segsum: the segment [{off}, {off} + {K} * {t}) leaves the row of n = {n}")
+    out = out_buffer("attn_segsum", out, (B, K), torch.float32, r, "r's device")
+    check(lib().koaf_attn_segsum(_ptr(r), _ptr(out), B, n, off, K, t, _stream()), "attn_segsum")
+    return out

@@ -96,7 +96,7 @@ def ablation_percent(attrs):
     return np.round(np.abs(t.numpy()) * 100., decimals=3)
 
 
-EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad")
+EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad", "attn_rollout", "attn_grad")
 
 
 def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None, explain_kwargs=None):
@@ -114,14 +114,19 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
     maps, ig_percent (ablation_percent of those) and ig_delta = the per-sample completeness residual sum_m ig_attrs - (F(x) -
     F(baseline)).  explain_fn="smoothgrad": sg_attrs = sum(x_m * map_m) of the run.smoothgrad maps and sg_percent.  Both hand
     their maps to the sink as "input_x_grad" does, and both pass `explain_kwargs` (a dict: n_steps, method, baselines, chunk /
-    n_samples, noise_level, seed, kind, chunk) to the function; the other keys take no keywords."""
+    n_samples, noise_level, seed, kind, chunk) to the function; the other keys take no keywords.
+    explain_fn="attn_rollout" | "attn_grad" (not in the reference; run/_attnrel.py): attn_attrs = the per-modality totals of the
+    attention relevance of the fusion transformers, attn_percent (ablation_percent of those) and attn_slice_scores -- per sample, one
+    list per modality of the K per-slice relevances.  The AttnRelevance tuples go to the sink.  explain_kwargs: `fuse` (rollout)."""
     if explain_fn not in EXPLAIN_FNS:
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
     kwargs = dict(explain_kwargs or {})
-    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad"):
+    attn_kw = explain_fn in ("attn_rollout", "attn_grad") and set(kwargs) == {"fuse"}
+    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad") and not attn_kw:
         raise ValueError(f"explain_fn {explain_fn} takes no explain_kwargs, got {sorted(kwargs)}")
     kwargs.pop("return_delta", None)
-    field = {"modal_abl": "modal_abl", "integrated_gradients": "ig", "smoothgrad": "sg"}.get(explain_fn, "ixg")
+    field = {"modal_abl": "modal_abl", "integrated_gradients": "ig", "smoothgrad": "sg", "attn_rollout": "attn",
+             "attn_grad": "attn"}.get(explain_fn, "ixg")
     acc = defaultdict(list)
     modals = list(modals)
     for batch in loader:
@@ -141,8 +146,15 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
             acc["modal_names"].extend([modals, ] * nb)
             acc["gradcam_slice_scores"].extend([[s[b] if s is not None else [] for s in scores] for b in range(nb)])
             continue
-        delta = None
-        if explain_fn == "modal_abl":
+        delta = scores = None
+        if explain_fn in ("attn_rollout", "attn_grad"):
+            from ._attnrel import attention_relevance
+            rel, totals, _ = attention_relevance(model, xs, ys.squeeze(), method=explain_fn[5:], **kwargs)
+            attrs = totals.to("cpu")
+            scores = [r.slices.to("cpu").numpy().tolist() for r in rel]
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, rel)
+        elif explain_fn == "modal_abl":
             attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
         elif explain_fn == "integrated_gradients":
             from ._attr import attribution_totals, integrated_gradients
@@ -166,6 +178,8 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
         acc["modal_names"].extend([modals, ] * attrs.shape[0])
         acc[f"{field}_attrs"].extend(attrs.numpy().tolist())
         acc[f"{field}_percent"].extend(ablation_percent(attrs).tolist())
+        if scores is not None:
+            acc["attn_slice_scores"].extend([[sc[b] for sc in scores] for b in range(attrs.shape[0])])
         if delta is not None:
             acc["ig_delta"].extend(delta.to("cpu").numpy().tolist())
     return dict(acc)
@@ -176,7 +190,7 @@ def ensemble_explain_foldw(raw_foldw, prefix="modal_abl"):
     per-fold columns modal_abl_attrs__k / modal_abl_percent__k, and modal_abl_percent = fold mean of the per-fold
     per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64).
     prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad"), "ig" / "sg"
-    for "integrated_gradients" / "smoothgrad"."""
+    for "integrated_gradients" / "smoothgrad", "attn" for "attn_rollout" / "attn_grad"."""
     folds = list(raw_foldw)
     if not folds:
         raise ValueError("no folds to ensemble")
