@@ -584,6 +584,37 @@ int koaf_path_points(const float* x, const float* base, float base_value, const 
 int koaf_attr_fold(float* acc, const float* g, const float* w, const float* x, const float* base, float base_value, int32_t J,
                    int32_t B, int64_t n, int32_t square, int32_t first, int32_t finish, void* stream);
 
+/* ---- Occlusion sensitivity maps (koaf_occl.hip; captum's Occlusion, named by the reference's recipe and never built there) -------
+ * An input row is a box of four extents dims[4] (an input of lower rank is padded IN FRONT with ones), win[4] the window and str[4]
+ * the strides, 1 <= str <= win <= dims: host arrays of four.  cnt[a] = 1 + ceil((dims[a] - win[a]) / str[a]) windows along
+ * dimension a; window k, flat and row-major over cnt with the last dimension fastest, covers [j str, min(j str + win, dims)) along
+ * every dimension (the last window is clipped).  K = prod cnt.  Rows and K stay below 2^31.  All four kernels are element-wise or
+ * row-wise, with no atomics and fixed orders: the bits do not depend on the grid.
+ *
+ * koaf_occl_points  out[j][b][i] = (i in window k0 + j) ? bs : x[b][i],  j in [0, J), k0 + J <= K;  bs = base[b][i], or base_value
+ *   when base is NULL.  x, base: [B][n], out: [J][B][n]; x and base are read once for all J.  16-byte accesses where n % 4 == 0 and
+ *   the pointers are aligned, one element per lane otherwise.  1 <= J <= KOAF_ATTR_MAX_J (the windows sit in LDS), B <= 65535.
+ * koaf_occl_slices  out[r] = the H x W slice image n of x with window k set to the baseline, (k, n) = rows[r] -- a device int32
+ *   table [nrows][2], n = b * K_img + kk: pixel (i, j) is element b*sb + kk*sk + i*si + j*sj of x, the strides of
+ *   koaf_cam_upsample, so out[r] is the image the slice fold of the occluded volume would hand the trunk.  Consecutive lanes walk
+ *   the unit-stride axis of the source: columns where sj == 1; where sk == 1 (the (B,1,R,C,S) volumes) 16 table rows x 64 pixels
+ *   pass through LDS, so that the read (consecutive table rows = consecutive slices of one sample, as run.occlusion lists them)
+ *   and the write are both coalesced.  A table row outside [0, K) x [0, B * K_img) is written as zeros, never read through.
+ * koaf_occl_rows  out[j][n] = src[j][n] in [0, F) ? fresh[src[j][n]] : cache[n];  cache [N], fresh [F], out [J][N] rows of
+ *   row_bytes bytes, row_bytes % 4 == 0 (a byte copy: fp32 and bf16 feature rows alike); src: device int32 [J][N], negative =
+ *   the cached row.
+ * koaf_occl_fold  out[b][i] = (sum of delta[k][b] over the windows k that cover element i, in ascending k, fp32) / their number
+ *   (one fp32 division; every element is covered, str <= win).  delta: [K][B].  No products: numpy's fp32 restates it bit for bit. */
+int koaf_occl_points(const float* x, const float* base, float base_value, float* out, int32_t J, int32_t B, const int32_t* dims,
+                     const int32_t* win, const int32_t* str, int32_t k0, void* stream);
+int koaf_occl_slices(const float* x, const float* base, float base_value, float* out, const int32_t* rows, int32_t nrows, int32_t B,
+                     const int32_t* dims, const int32_t* win, const int32_t* str, int32_t K_img, int32_t H, int32_t W, int64_t sb,
+                     int64_t sk, int64_t si, int64_t sj, void* stream);
+int koaf_occl_rows(const void* cache, const void* fresh, const int32_t* src, void* out, int32_t J, int32_t N, int32_t F,
+                   int64_t row_bytes, void* stream);
+int koaf_occl_fold(const float* delta, float* out, int32_t K, int32_t B, const int32_t* dims, const int32_t* win, const int32_t* str,
+                   void* stream);
+
 /* ---- Attention relevance of the FeaT fusion: rollout and the gradient-weighted rule (koaf_attnrel.hip; not in the reference) ----
  * All tensors are contiguous fp32, any n, h, d >= 1 (tiles are guarded, nothing needs a multiple).  Full fp32 products; sums in a
  * fixed order in fp32 or fp64; no atomics: run-to-run identical bits.  Outputs may not overlap inputs (refused).

@@ -1,5 +1,7 @@
 """Explanations: class-activation maps (koaf_cam.hip), the path attributions -- integrated gradients, SmoothGrad
-(koaf_attr.hip) -- and the attention relevance of the fusion transformers (koaf_attnrel.hip)."""
+(koaf_attr.hip) --, the occlusion maps (koaf_occl.hip) and the attention relevance of the fusion transformers (koaf_attnrel.hip)."""
+import ctypes
+
 import torch
 
 from .._lib import KoafError, check, defines, lib
@@ -97,6 +99,87 @@ def attr_fold(acc, g, w, square=False, first=False, x=None, base=None):
     check(lib().koaf_attr_fold(_ptr(acc), _ptr(g), _ptr(w), _ptr(x), _ptr(bt), bv, J, B, n, 1 if square else 0, 1 if first else 0,
                                1 if x is not None else 0, _stream()), "attr_fold")
     return acc
+
+
+# ------------------------------------------------------------------------------------------------
+# occlusion sensitivity maps (koaf_occl.hip)
+# ------------------------------------------------------------------------------------------------
+def _occl_box(what, shape, window, strides):
+    """the three host arrays of four the entry points take, from the extents behind the batch dimension (padded in front with
+    ones)"""
+    dims = tuple(int(d) for d in shape)
+    window, strides = tuple(int(w) for w in window), tuple(int(s) for s in strides)
+    if not 1 <= len(dims) <= 4 or len(window) != len(dims) or len(strides) != len(dims):
+        raise KoafError(f"{what}: one to four extents behind the batch dimension, a window and strides of that rank, got {dims}, "
+                        f"{window}, {strides}")
+    if not all(1 <= s <= w <= d for d, w, s in zip(dims, window, strides)):
+        raise KoafError(f"{what}: 1 <= strides <= window <= extents, got {strides}, {window}, {dims}")
+    pad = (1,) * (4 - len(dims))
+    return tuple((ctypes.c_int32 * 4)(*(pad + v)) for v in (dims, window, strides))
+
+
+def occl_points(x, window, strides, k0, J, base=None):
+    """out[j] = x with window k0 + j set to the baseline -> [J, *x.shape] (koaf_occl_points: x and base read once for all J).
+    window / strides: one entry per dimension of x behind the batch; base as in path_points."""
+    B, n, bt, bv = _attr_rows("occl_points", x, base)
+    dims, win, st = _occl_box("occl_points", x.shape[1:], window, strides)
+    out = torch.empty((int(J),) + tuple(x.shape), device=x.device, dtype=torch.float32)
+    check(lib().koaf_occl_points(_ptr(x), _ptr(bt), bv, _ptr(out), int(J), B, dims, win, st, int(k0), _stream()), "occl_points")
+    return out
+
+
+def occl_slices(x, rows, window, strides, K_img, H, W, img_strides, base=None):
+    """[nrows, 1, H, W]: image n of x with window k set to the baseline for every (k, n) of the device int32 table rows [nrows, 2],
+    n = b * K_img + kk; img_strides = (sb, sk, si, sj) as run.cam_strides gives them (koaf_occl_slices: what the slice fold of
+    the occluded input would hand the trunk, gathered straight from x)."""
+    B, n, bt, bv = _attr_rows("occl_slices", x, base)
+    dims, win, st = _occl_box("occl_slices", x.shape[1:], window, strides)
+    check_tensor("occl_slices", "rows", rows, torch.int32, like=x, nonempty=True, where="x's device")
+    if rows.dim() != 2 or rows.shape[1] != 2:
+        raise KoafError(f"occl_slices: rows is [nrows, 2], got {tuple(rows.shape)}")
+    sb, sk, si, sj = (int(s) for s in img_strides)
+    out = torch.empty((int(rows.shape[0]), 1, int(H), int(W)), device=x.device, dtype=torch.float32)
+    check(lib().koaf_occl_slices(_ptr(x), _ptr(bt), bv, _ptr(out), _ptr(rows), int(rows.shape[0]), B, dims, win, st, int(K_img), int(H),
+                                 int(W), sb, sk, si, sj, _stream()), "occl_slices")
+    return out
+
+
+def occl_rows(cache, fresh, src):
+    """out [J, N, ...]: out[j][n] = fresh[src[j][n]] where src[j][n] >= 0, else cache[n] (koaf_occl_rows: a byte copy of whole
+    rows).  cache [N, ...] and fresh [F, ...] are contiguous, of one dtype and one row shape; fresh may be None (F = 0);
+    src: device int32 [J, N]."""
+    if not torch.is_tensor(cache) or not cache.is_contiguous() or cache.dim() < 1 or cache.numel() == 0:
+        raise KoafError("occl_rows: cache is a contiguous, non-empty tensor [N, ...]")
+    N = int(cache.shape[0])
+    row_bytes = cache.numel() // N * cache.element_size()
+    F = 0
+    if fresh is not None:
+        if not fresh.is_contiguous() or fresh.dtype != cache.dtype or fresh.device != cache.device or tuple(fresh.shape[1:]) != tuple(cache.shape[1:]):
+            raise KoafError(f"occl_rows: fresh is contiguous [F, *{tuple(cache.shape[1:])}] {cache.dtype} on cache's device, got "
+                            f"{tuple(fresh.shape)} {fresh.dtype}")
+        F = int(fresh.shape[0])
+    check_tensor("occl_rows", "src", src, torch.int32, like=cache, nonempty=True, where="cache's device")
+    if src.dim() != 2 or src.shape[1] != N:
+        raise KoafError(f"occl_rows: src is [J, {N}], got {tuple(src.shape)}")
+    if row_bytes % 4:
+        raise KoafError(f"occl_rows: rows of {row_bytes} bytes are no multiple of 4")
+    J = int(src.shape[0])
+    out = torch.empty((J,) + tuple(cache.shape), device=cache.device, dtype=cache.dtype)
+    check(lib().koaf_occl_rows(_ptr(cache), _ptr(fresh) if F else None, _ptr(src), _ptr(out), J, N, F, row_bytes, _stream()), "occl_rows")
+    return out
+
+
+def occl_fold(delta, shape, window, strides):
+    """the occlusion map [B, *shape] of the score differences delta [K, B]: per element the mean of delta[k] over the windows that
+    cover it, summed in ascending k (koaf_occl_fold).  shape / window / strides: the extents behind the batch dimension."""
+    check_tensor("occl_fold", "delta", delta, torch.float32, nonempty=True)
+    if delta.dim() != 2:
+        raise KoafError(f"occl_fold: delta is [K, B], got {tuple(delta.shape)}")
+    dims, win, st = _occl_box("occl_fold", shape, window, strides)
+    K, B = (int(s) for s in delta.shape)
+    out = torch.empty((B,) + tuple(int(d) for d in shape), device=delta.device, dtype=torch.float32)
+    check(lib().koaf_occl_fold(_ptr(delta), _ptr(out), K, B, dims, win, st, _stream()), "occl_fold")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

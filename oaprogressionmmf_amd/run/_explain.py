@@ -13,7 +13,7 @@ explain_epoch(explain_fn="input_x_grad") accumulates the per-modality totals sum
 what the ablation measures with M + 1 forwards.  Class-activation maps (run/_gradcam.py): explain_epoch(explain_fn="gradcam")
 accumulates the per-slice map sums and hands the Grad-CAM volumes to the sink.  Path attributions (run/_attr.py):
 explain_epoch(explain_fn="integrated_gradients" | "smoothgrad") accumulates the per-modality totals of the maps and hands the
-maps to the sink."""
+maps to the sink.  Occlusion maps (run/_occlusion.py): explain_epoch(explain_fn="occlusion"), in the same way."""
 from collections import defaultdict
 
 import numpy as np
@@ -96,7 +96,7 @@ def ablation_percent(attrs):
     return np.round(np.abs(t.numpy()) * 100., decimals=3)
 
 
-EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad", "attn_rollout", "attn_grad")
+EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad", "attn_rollout", "attn_grad", "occlusion")
 
 
 def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None, explain_kwargs=None):
@@ -117,16 +117,20 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
     n_samples, noise_level, seed, kind, chunk) to the function; the other keys take no keywords.
     explain_fn="attn_rollout" | "attn_grad" (not in the reference; run/_attnrel.py): attn_attrs = the per-modality totals of the
     attention relevance of the fusion transformers, attn_percent (ablation_percent of those) and attn_slice_scores -- per sample, one
-    list per modality of the K per-slice relevances.  The AttnRelevance tuples go to the sink.  explain_kwargs: `fuse` (rollout)."""
+    list per modality of the K per-slice relevances.  The AttnRelevance tuples go to the sink.  explain_kwargs: `fuse` (rollout).
+    explain_fn="occlusion" (the recipe's third key; run/_occlusion.py): occl_attrs = the per-modality sums of the run.occlusion maps
+    (0 for an input whose window is None) and occl_percent (ablation_percent of those).  The maps go to the sink as the other map
+    keys' do.  explain_kwargs: sliding_window_shapes (required), strides, baselines, chunk, sparse."""
     if explain_fn not in EXPLAIN_FNS:
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
     kwargs = dict(explain_kwargs or {})
     attn_kw = explain_fn in ("attn_rollout", "attn_grad") and set(kwargs) == {"fuse"}
-    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad") and not attn_kw:
+    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad", "occlusion") and not attn_kw:
         raise ValueError(f"explain_fn {explain_fn} takes no explain_kwargs, got {sorted(kwargs)}")
     kwargs.pop("return_delta", None)
+    kwargs.pop("return_deltas", None)
     field = {"modal_abl": "modal_abl", "integrated_gradients": "ig", "smoothgrad": "sg", "attn_rollout": "attn",
-             "attn_grad": "attn"}.get(explain_fn, "ixg")
+             "attn_grad": "attn", "occlusion": "occl"}.get(explain_fn, "ixg")
     acc = defaultdict(list)
     modals = list(modals)
     for batch in loader:
@@ -168,6 +172,12 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
             attrs = input_x_grad_totals(xs, maps).to("cpu")
             if sink is not None:
                 sink(list(batch[("-", "exam_knee_id")]), modals, maps)
+        elif explain_fn == "occlusion":
+            from ._occlusion import occlusion, occlusion_totals
+            maps = occlusion(model, xs, ys.squeeze(), **kwargs)
+            attrs = occlusion_totals(maps, xs).to("cpu")
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, maps)
         else:
             grads = input_gradients(model, xs, ys.squeeze())
             attrs = input_x_grad_totals(xs, grads).to("cpu")
@@ -190,7 +200,7 @@ def ensemble_explain_foldw(raw_foldw, prefix="modal_abl"):
     per-fold columns modal_abl_attrs__k / modal_abl_percent__k, and modal_abl_percent = fold mean of the per-fold
     per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64).
     prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad"), "ig" / "sg"
-    for "integrated_gradients" / "smoothgrad", "attn" for "attn_rollout" / "attn_grad"."""
+    for "integrated_gradients" / "smoothgrad", "attn" for "attn_rollout" / "attn_grad", "occl" for "occlusion"."""
     folds = list(raw_foldw)
     if not folds:
         raise ValueError("no folds to ensemble")
