@@ -191,7 +191,7 @@ int koaf_gemm_pick_tile(const KoafGemm* g, int32_t* bm, int32_t* bn);
 int koaf_gemm_part_rows(const KoafGemm* g);
 /* Launch record (tests; off by default): which kernel variant served each koaf_gemm call.  While switched on, every koaf_gemm
  * launch appends one entry -- plain host memory, written before the launch; no device work, nothing when off.  `variant` is the
- * tag koaf_gemm reports launch errors under ("koaf_gemm", "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"; "koaf_wgrad3/ring": the 3x3 weight-gradient ring kernel
+ * tag koaf_gemm reports launch errors under ("koaf_gemm", "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"; "koaf_fwd1": the 256-row kernel of the dense 1x1 forward convolutions; "koaf_wgrad3/ring": the 3x3 weight-gradient ring kernel
  * behind koaf_conv2d_wgrad leaves an entry too -- 64 x 64 tiles, splitk = its k-ranges, K = the padded positions); `tiles` the
  * block tiles of one (split, batch) slice and `grid_x` the blocks launched for them (grid_x < tiles: persistent blocks that walk
  * several tiles).  A convolution entry point that issues several GEMMs (a stride-2 data gradient: one per phase) leaves one

@@ -134,6 +134,29 @@ static inline bool fwd_s2_ok(const KoafGemm& g, int KH, int KW, int stride, int 
     return (int64_t)(g.M / (A.PH * A.PW)) * A.H * A.W < (1ll << 31);
 }
 
+// koaf_fwd1.hip: the dense 1x1 / stride-1 forward convolutions over the fp32 tensors on 256-row tiles, bit-identical to koaf_gemm_kernel on
+// the same descriptor; koaf_fwd1_form: the form a (Cin, Cout) ships in (0 one tile per block, 1 the persistent walk), -1 for none
+int koaf_fwd1(const KoafGemm& g, int form, void* stream);
+int koaf_fwd1_form(int K, int N);
+bool koaf_stream_on();      // koaf_gemm.hip: koaf_set_stream's switch
+// the form in which koaf_fwd1 takes the forward convolution described by g, -1 if it does not.  A pointwise call of the fp16 scheme with
+// the F plane image, fp32 tensors at pixel stride Cin, no plane-image input, tail or emission, whole k-tiles and at least two of them
+// (Cin % 32 == 0, K >= 64), whole column tiles (Cout % 128 == 0), 16-B aligned pointers, behind a prologue no more channels than the
+// coefficient table holds (1024), the streamed kernels switched on (koaf_set_stream(0) keeps these calls on the block-wide loader) --
+// and whole 256-row tiles, at least one per CU (M % 256 == 0, M >= 65536): below that a 256-row tiling cannot fill the chip, and the
+// small calls the tests pin to koaf_gemm/stream from their launch records stay there.  Among these, the (Cin, Cout) of koaf_fwd1_form's
+// table: the production shapes that passed the per-call rule.
+static inline int fwd1_ok(const KoafGemm& g, int KH, int KW, int stride, int pad, bool x_planes, bool tail, bool emit) {
+    const KoafOperand& A = g.A;
+    if (!is_pointwise(KH, KW, stride, pad) || !koaf_stream_on()) return -1;
+    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || g.act16 != 0 || x_planes || tail || emit) return -1;
+    if (A.kind != 0 || A.gather != 0 || A.amax || A.ld != g.K || (g.K % 32) != 0 || g.K < 64 || (g.N % 128) != 0) return -1;
+    if ((g.M % 256) != 0 || g.M < 65536) return -1;
+    if (A.tf != 0 && (A.tf != 1 || g.K > 1024 || !aligned16(A.sc) || !aligned16(A.sh))) return -1;
+    if (!aligned16(A.ptr) || !aligned16(g.B.planes) || !aligned16(g.C)) return -1;
+    return koaf_fwd1_form(g.K, g.N);
+}
+
 extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t N, int32_t H, int32_t W, int32_t Cin,
                                int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* in_sc,
                                const float* in_sh, float* stats, int32_t* stats_rows, const float* stats_shift,
@@ -179,6 +202,10 @@ extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t
     if (fwd_s2_ok(g, KH, KW, stride, pad, x_planes != nullptr, tail != nullptr, emit != nullptr)) {
         if (stats_rows) *stats_rows = g.M / 128;        // two partial rows per 256-row tile: the rows of a 128-row tiling
         return koaf_fwd_s2(g, stream);
+    }
+    if (const int form = fwd1_ok(g, KH, KW, stride, pad, x_planes != nullptr, tail != nullptr, emit != nullptr); form >= 0) {
+        if (stats_rows) *stats_rows = g.M / 128;
+        return koaf_fwd1(g, form, stream);
     }
     if (stats_rows) *stats_rows = koaf_gemm_part_rows(&g);
     return koaf_gemm(&g, stream);

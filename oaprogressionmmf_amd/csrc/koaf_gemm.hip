@@ -123,6 +123,9 @@ bool stream_ok(const KoafGemm& g) {
 }
 }  // namespace
 
+// koaf_set_stream's switch for the dispatch rules outside this file (koaf_conv.hip fwd1_ok)
+bool koaf_stream_on() { return g_stream_mode == 1; }
+
 extern "C" int koaf_gemm_pick_tile(const KoafGemm* g, int32_t* bm, int32_t* bn) {
     int b_m = g->bm, b_n = g->bn;
     const int64_t batch = (int64_t)g->nb0 * g->nb1 * (g->splitk > 0 ? g->splitk : 1);

@@ -62,7 +62,8 @@ def launch_log(on):
 
 def launch_log_read():
     """the launches recorded since launch_log(True): one dict per koaf_gemm launch, in launch order -- variant ("koaf_gemm",
-    "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"; "koaf_wgrad3/ring": the 3x3 weight-gradient ring kernel, splitk = its
+    "koaf_gemm/stream", "/emit", "/halo", "/halo128", "/t2d"; "koaf_fwd1": the 256-row kernel of the dense 1x1 forward convolutions,
+    grid_x = min(tiles, 256) where its blocks walk; "koaf_wgrad3/ring": the 3x3 weight-gradient ring kernel, splitk = its
     k-ranges), bm, bn, tiles, grid_x (< tiles: persistent blocks walk), splitk, nbatch, fmt, a_tf, b_tf, act16, M, N, K, emit"""
     L = lib()
     n = min(L.koaf_launch_log_read(None, 0), 4096)        # (launches seen; the record keeps the first 4096)
