@@ -639,6 +639,32 @@ int koaf_attn_apply(const float* r_in, const float* abar, float* r_out, int32_t 
                     void* stream);
 int koaf_attn_segsum(const float* r, float* out, int32_t B, int32_t n, int32_t off, int32_t K, int32_t t, void* stream);
 
+/* ---- Modality coalitions and their Shapley values (koaf_coal.hip; not in the reference) ------------------------------------------
+ * A coalition is a bit mask over the M inputs of a fusion model, bit i set = input i present; 1 <= M <= KOAF_COAL_MAX_M.
+ *
+ * koaf_coal_tokens  out[j][b][l][:] = (masks[j] >> seg(l) & 1) ? tx[b][l][:] : t0[b % B0][l][:] -- the final FeaT's input tokens of
+ *   coalition j, spliced from the tokens of the intact inputs tx [B][L][D] and of the baselines t0 [B0][L][D], B0 == 1 (one
+ *   baseline row for every sample) or B0 == B;  out: [J][B][L][D], all fp32.  seg_off: HOST int32 [M + 1], seg_off[0] == 0 <
+ *   seg_off[1] < ... < seg_off[M] == L: token l belongs to input seg(l) = i where seg_off[i] <= l < seg_off[i + 1].  masks: HOST
+ *   uint32 [J], J >= 1, no bit at or above M.  Both tables travel as kernel arguments (KOAF_COAL_MAX_J masks a launch), so every
+ *   refusal comes ahead of the first launch.  tx and t0 are read once per launch for all of its coalitions; 16-byte accesses where
+ *   L * D % 4 == 0 and the pointers are aligned, one element per lane otherwise.  A copy: no value changes.  L * D < 2^31,
+ *   B <= 65535.
+ * koaf_shapley_fold  from the coalition values v [S][B] (fp32, S == 2^M, row s = the coalition with mask s), in fp64, one thread
+ *   per output element, the subsets T taken in ascending mask order (|T| = its number of players):
+ *     phi[b][i]      = sum over T without i     of w_phi[|T|] * (v[T + i] - v[T]),                      w_phi[t] = t! (M - t - 1)! / M!
+ *     inter[b][i][j] = sum over T without i, j  of w_int[|T|] * (v[T + i + j] - v[T + i] - v[T + j] + v[T]),
+ *                      w_int[t] = t! (M - t - 2)! / (M - 1)!;  inter[b][i][i] = 0, and at M == 1 all of it is 0
+ *     loo[b][i]      = v[N] - v[N - i],   solo[b][i] = v[{i}] - v[{}]
+ *   w_phi: HOST fp64 [M];  w_int: HOST fp64 [M - 1] (NULL at M == 1): the caller's table, the kernel does no factorial arithmetic.
+ *   phi, loo, solo: [B][M];  inter: [B][M][M], all fp64. */
+#define KOAF_COAL_MAX_M 8
+#define KOAF_COAL_MAX_J 64
+int koaf_coal_tokens(const float* tx, const float* t0, const int32_t* seg_off, const uint32_t* masks, float* out, int32_t J, int32_t B,
+                     int32_t B0, int32_t L, int32_t D, int32_t M, void* stream);
+int koaf_shapley_fold(const float* v, const double* w_phi, const double* w_int, double* phi, double* inter, double* loo, double* solo,
+                      int32_t S, int32_t B, int32_t M, void* stream);
+
 /* ---- Input plumbing -------------------------------------------------------------------------- */
 /* "b ch r c s -> (b s) ch r c" (_xrNmrMcP.py:209-210): x [B,R,C,S] -> out [B*S,R,C] */
 int koaf_slice_fold(const float* x, float* out, int32_t B, int32_t R, int32_t Cc, int32_t S,

@@ -25,8 +25,9 @@ from .conv import (ACT_SCALE, CONV_F16, _dy_planes, _img, _rup, _slab_ws, act_pl
                    wplanes_build)
 from .dense import (add, attention_bwd, attention_fwd, colsum, counter_add, dropout, dropout2d, gelu_bwd, gelu_fwd, layernorm_bwd,
                     layernorm_fwd, linear_dgrad, linear_fwd, linear_wgrad, relu_bwd, relu_fwd, softmax_rows_)
-from .explain import (ATTN_MODES, ATTR_MAX_J, CAM_NORMALIZE, _attr_coefs, _attr_rows, attn_apply, attn_layer, attn_segsum, attr_fold, cam,
-                      cam_upsample, occl_fold, occl_points, occl_rows, occl_slices, path_points)
+from .explain import (ATTN_MODES, ATTR_MAX_J, CAM_NORMALIZE, COAL_MAX_M, _attr_coefs, _attr_rows, attn_apply, attn_layer, attn_segsum,
+                      attr_fold, cam, cam_upsample, coal_tokens, occl_fold, occl_points, occl_rows, occl_slices, path_points, shapley_fold,
+                      shapley_weights)
 from .inputs import (HostWindowTable, _STORED, _WIDEN, _upload_bytes, _window_ws, augment, downscale2, input_pipeline, minmax, resize,
                      rowdot, slice_fold, slice_unfold, widen, window_minmax, window_rows, window_table)
 from .metrics import (METRICS_FLAG_TEXT, METRICS_MAX_N, _metric_scores, confusion, curve_metrics, curve_points, curve_points_len,

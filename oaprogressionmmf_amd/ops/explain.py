@@ -1,5 +1,6 @@
 """Explanations: class-activation maps (koaf_cam.hip), the path attributions -- integrated gradients, SmoothGrad
-(koaf_attr.hip) --, the occlusion maps (koaf_occl.hip) and the attention relevance of the fusion transformers (koaf_attnrel.hip)."""
+(koaf_attr.hip) --, the occlusion maps (koaf_occl.hip), the modality coalitions and their Shapley values (koaf_coal.hip) and the
+attention relevance of the fusion transformers (koaf_attnrel.hip)."""
 import ctypes
 
 import torch
@@ -180,6 +181,77 @@ def occl_fold(delta, shape, window, strides):
     out = torch.empty((B,) + tuple(int(d) for d in shape), device=delta.device, dtype=torch.float32)
     check(lib().koaf_occl_fold(_ptr(delta), _ptr(out), K, B, dims, win, st, _stream()), "occl_fold")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# modality coalitions and their Shapley values (koaf_coal.hip)
+# ------------------------------------------------------------------------------------------------
+COAL_MAX_M = defines()["KOAF_COAL_MAX_M"]
+
+
+def _host_ints(what, name, seq):
+    """a host table (a sequence, a numpy array or a CPU tensor of integers) as a list of python ints"""
+    try:
+        vals = seq.tolist() if hasattr(seq, "tolist") else list(seq)
+        if any(isinstance(v, bool) or int(v) != v for v in vals):
+            raise TypeError
+        return [int(v) for v in vals]
+    except (TypeError, ValueError, RuntimeError):
+        raise KoafError(f"{what}: {name} is a host sequence of integers, got {type(seq).__name__}") from None
+
+
+def coal_tokens(tx, t0, seg_off, masks, out=None):
+    """out [J, B, L, D]: out[j, b, l] = tx[b, l] where bit seg(l) of masks[j] is set, else t0[b % B0, l] (koaf_coal_tokens: the
+    final FeaT's input tokens of J coalitions; tx and t0 read once for all of them, no value changed).  tx [B, L, D], t0 [B0, L, D]
+    with B0 in (1, B): fp32 on one device.  seg_off: host integers [M + 1], 0 = seg_off[0] < ... < seg_off[M] = L -- token l is
+    input i's where seg_off[i] <= l < seg_off[i + 1]; masks: host integers [J], one bit per input, none at or above M <= COAL_MAX_M."""
+    check_tensor("coal_tokens", "tx", tx, torch.float32, nonempty=True)
+    if tx.dim() != 3:
+        raise KoafError(f"coal_tokens: tx is [B, L, D], got {tuple(tx.shape)}")
+    B, L, D = (int(s) for s in tx.shape)
+    check_tensor("coal_tokens", "t0", t0, torch.float32, like=tx, nonempty=True, where="tx's device")
+    if t0.dim() != 3 or tuple(t0.shape[1:]) != (L, D) or int(t0.shape[0]) not in (1, B):
+        raise KoafError(f"coal_tokens: t0 is [1 | {B}, {L}, {D}], got {tuple(t0.shape)}")
+    seg, msk = _host_ints("coal_tokens", "seg_off", seg_off), _host_ints("coal_tokens", "masks", masks)
+    M, J = len(seg) - 1, len(msk)
+    if not 1 <= M <= COAL_MAX_M or J < 1:
+        raise KoafError(f"coal_tokens: seg_off holds M + 1 offsets, 1 <= M <= {COAL_MAX_M}, and masks at least one coalition, got "
+                        f"{len(seg)} offsets and {J} masks")
+    if seg[0] != 0 or seg[M] != L or any(a >= b for a, b in zip(seg, seg[1:])):
+        raise KoafError(f"coal_tokens: seg_off ascends strictly from 0 to L = {L}, got {seg}")
+    if any(not 0 <= m < (1 << M) for m in msk):
+        raise KoafError(f"coal_tokens: a mask has one bit per input, none at or above M = {M}, got {msk}")
+    out = out_buffer("coal_tokens", out, (J, B, L, D), torch.float32, tx, "tx's device")
+    check(lib().koaf_coal_tokens(_ptr(tx), _ptr(t0), (ctypes.c_int32 * (M + 1))(*seg), (ctypes.c_uint32 * J)(*msk), _ptr(out), J, B,
+                                 int(t0.shape[0]), L, D, M, _stream()), "coal_tokens")
+    return out
+
+
+def shapley_weights(M):
+    """(w_phi [M], w_int [M - 1]) as python floats: w_phi[t] = t! (M - t - 1)! / M!, w_int[t] = t! (M - t - 2)! / (M - 1)!, each one
+    correctly rounded quotient of two integers"""
+    from math import factorial as f
+    M = int(M)
+    return [f(t) * f(M - t - 1) / f(M) for t in range(M)], [f(t) * f(M - t - 2) / f(M - 1) for t in range(M - 1)]
+
+
+def shapley_fold(v, M):
+    """(phi [B, M], inter [B, M, M], loo [B, M], solo [B, M]), fp64 device tensors, of the coalition values v [2^M, B] (fp32; row s
+    = the coalition whose bit i says player i is present): the Shapley values, the Shapley interaction index (zero diagonal),
+    v(N) - v(N - i) and v({i}) - v({}) (koaf_shapley_fold: fp64, subsets in ascending mask order)."""
+    M = int(M)
+    if not 1 <= M <= COAL_MAX_M:
+        raise KoafError(f"shapley_fold: 1 <= M <= {COAL_MAX_M}, got M = {M}")
+    check_tensor("shapley_fold", "v", v, torch.float32, nonempty=True)
+    if v.dim() != 2 or v.shape[0] != 1 << M:
+        raise KoafError(f"shapley_fold: v is [2^M = {1 << M}, B], got {tuple(v.shape)}")
+    S, B = (int(s) for s in v.shape)
+    wp, wi = shapley_weights(M)
+    phi, loo, solo = (torch.empty((B, M), device=v.device, dtype=torch.float64) for _ in range(3))
+    inter = torch.empty((B, M, M), device=v.device, dtype=torch.float64)
+    check(lib().koaf_shapley_fold(_ptr(v), (ctypes.c_double * M)(*wp), (ctypes.c_double * (M - 1))(*wi) if M > 1 else None, _ptr(phi),
+                                  _ptr(inter), _ptr(loo), _ptr(solo), S, B, M, _stream()), "shapley_fold")
+    return phi, inter, loo, solo
 
 
 # ------------------------------------------------------------------------------------------------

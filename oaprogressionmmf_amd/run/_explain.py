@@ -13,7 +13,8 @@ explain_epoch(explain_fn="input_x_grad") accumulates the per-modality totals sum
 what the ablation measures with M + 1 forwards.  Class-activation maps (run/_gradcam.py): explain_epoch(explain_fn="gradcam")
 accumulates the per-slice map sums and hands the Grad-CAM volumes to the sink.  Path attributions (run/_attr.py):
 explain_epoch(explain_fn="integrated_gradients" | "smoothgrad") accumulates the per-modality totals of the maps and hands the
-maps to the sink.  Occlusion maps (run/_occlusion.py): explain_epoch(explain_fn="occlusion"), in the same way."""
+maps to the sink.  Occlusion maps (run/_occlusion.py): explain_epoch(explain_fn="occlusion"), in the same way.  Modality Shapley
+values (run/_coalitions.py): explain_epoch(explain_fn="modal_shapley") accumulates them with their interactions."""
 from collections import defaultdict
 
 import numpy as np
@@ -96,7 +97,8 @@ def ablation_percent(attrs):
     return np.round(np.abs(t.numpy()) * 100., decimals=3)
 
 
-EXPLAIN_FNS = ("modal_abl", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad", "attn_rollout", "attn_grad", "occlusion")
+EXPLAIN_FNS = ("modal_abl", "modal_shapley", "input_x_grad", "gradcam", "integrated_gradients", "smoothgrad", "attn_rollout", "attn_grad",
+               "occlusion")
 
 
 def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_fn="modal_abl", sink=None, explain_kwargs=None):
@@ -120,17 +122,22 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
     list per modality of the K per-slice relevances.  The AttnRelevance tuples go to the sink.  explain_kwargs: `fuse` (rollout).
     explain_fn="occlusion" (the recipe's third key; run/_occlusion.py): occl_attrs = the per-modality sums of the run.occlusion maps
     (0 for an input whose window is None) and occl_percent (ablation_percent of those).  The maps go to the sink as the other map
-    keys' do.  explain_kwargs: sliding_window_shapes (required), strides, baselines, chunk, sparse."""
+    keys' do.  explain_kwargs: sliding_window_shapes (required), strides, baselines, chunk, sparse.
+    explain_fn="modal_shapley" (not in the reference; run/_coalitions.py): shap_attrs = the Shapley values of the modalities (or of
+    the `players`) over the 2^P coalitions of inputs, shap_percent (ablation_percent of those), shap_interactions (per sample the
+    P x P Shapley interaction index), shap_loo = v(N) - v(N - i), shap_solo = v({i}) - v({}) and shap_delta = the per-sample
+    efficiency residual sum_i phi_i - (v(N) - v({})).  The ModalShapley tuples go to the sink.  explain_kwargs: baselines, players,
+    chunk, sparse."""
     if explain_fn not in EXPLAIN_FNS:
         raise ValueError(f"Unknown explain_fn: {explain_fn}")
     kwargs = dict(explain_kwargs or {})
     attn_kw = explain_fn in ("attn_rollout", "attn_grad") and set(kwargs) == {"fuse"}
-    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad", "occlusion") and not attn_kw:
+    if kwargs and explain_fn not in ("integrated_gradients", "smoothgrad", "occlusion", "modal_shapley") and not attn_kw:
         raise ValueError(f"explain_fn {explain_fn} takes no explain_kwargs, got {sorted(kwargs)}")
     kwargs.pop("return_delta", None)
     kwargs.pop("return_deltas", None)
     field = {"modal_abl": "modal_abl", "integrated_gradients": "ig", "smoothgrad": "sg", "attn_rollout": "attn",
-             "attn_grad": "attn", "occlusion": "occl"}.get(explain_fn, "ixg")
+             "attn_grad": "attn", "occlusion": "occl", "modal_shapley": "shap"}.get(explain_fn, "ixg")
     acc = defaultdict(list)
     modals = list(modals)
     for batch in loader:
@@ -150,7 +157,7 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
             acc["modal_names"].extend([modals, ] * nb)
             acc["gradcam_slice_scores"].extend([[s[b] if s is not None else [] for s in scores] for b in range(nb)])
             continue
-        delta = scores = None
+        delta = scores = shap = None
         if explain_fn in ("attn_rollout", "attn_grad"):
             from ._attnrel import attention_relevance
             rel, totals, _ = attention_relevance(model, xs, ys.squeeze(), method=explain_fn[5:], **kwargs)
@@ -160,6 +167,12 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
                 sink(list(batch[("-", "exam_knee_id")]), modals, rel)
         elif explain_fn == "modal_abl":
             attrs = modal_ablation(model, xs, ys.squeeze()).to("cpu")
+        elif explain_fn == "modal_shapley":
+            from ._coalitions import modal_shapley
+            shap = modal_shapley(model, xs, ys.squeeze(), **kwargs)
+            attrs = shap.phi.float().to("cpu")
+            if sink is not None:
+                sink(list(batch[("-", "exam_knee_id")]), modals, shap)
         elif explain_fn == "integrated_gradients":
             from ._attr import attribution_totals, integrated_gradients
             maps, delta = integrated_gradients(model, xs, ys.squeeze(), return_delta=True, **kwargs)
@@ -190,6 +203,11 @@ def explain_epoch(model, loader, modals, downscale=None, device="cuda", explain_
         acc[f"{field}_percent"].extend(ablation_percent(attrs).tolist())
         if scores is not None:
             acc["attn_slice_scores"].extend([[sc[b] for sc in scores] for b in range(attrs.shape[0])])
+        if shap is not None:
+            acc["shap_interactions"].extend(shap.interaction.to("cpu").numpy().tolist())
+            acc["shap_loo"].extend(shap.loo.to("cpu").numpy().tolist())
+            acc["shap_solo"].extend(shap.solo.to("cpu").numpy().tolist())
+            acc["shap_delta"].extend((shap.phi.sum(dim=1) - (shap.v_full.double() - shap.v_empty.double())).to("cpu").numpy().tolist())
         if delta is not None:
             acc["ig_delta"].extend(delta.to("cpu").numpy().tolist())
     return dict(acc)
@@ -200,7 +218,8 @@ def ensemble_explain_foldw(raw_foldw, prefix="modal_abl"):
     per-fold columns modal_abl_attrs__k / modal_abl_percent__k, and modal_abl_percent = fold mean of the per-fold
     per-cent rows renormalised to sum 1 (a fraction, as the reference leaves it; float64).
     prefix: the field family to merge -- "modal_abl" (the reference's), or "ixg" for explain_epoch(explain_fn="input_x_grad"), "ig" / "sg"
-    for "integrated_gradients" / "smoothgrad", "attn" for "attn_rollout" / "attn_grad", "occl" for "occlusion"."""
+    for "integrated_gradients" / "smoothgrad", "attn" for "attn_rollout" / "attn_grad", "occl" for "occlusion", "shap" for
+    "modal_shapley"."""
     folds = list(raw_foldw)
     if not folds:
         raise ValueError("no folds to ensemble")
