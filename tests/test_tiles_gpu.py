@@ -62,8 +62,8 @@ D5 = (245, 10, 10, 256, 1024, 1, 1, 0)     # N = 256, K = 1024: 384 tiles, rows 
 # 411 tiles each) and the 1x1 downsample 256 -> 512 (forward 776 tiles: walks; data gradient: one class has the tap, 388 tiles)
 S3 = (53, 63, 61, 128, 128, 3, 2, 1)
 S1 = (25, 63, 61, 256, 512, 1, 2, 0)
-# 3x3 / stride 1 beside test_activation_plane_images: W = 78 with odd H (layer1 of the 310^2 radiograph: the 128-row halo kernel, not
-# the rectangle one) and the halo kernels' width limit at 128 output columns, W = 64 (halo, 256 rows) | 65 (per-tap gather)
+# 3x3 / stride 1 beside test_activation_plane_images (the family's own table, both orientations, per tile: test_conv3_edges_gpu.py):
+# W = 78 with odd H (layer1 of the 310^2 radiograph: the 128-row halo kernel, not the rectangle one) and the halo kernels' width limit at 128 output columns, W = 64 (halo, 256 rows) | 65 (per-tap gather)
 W78 = (2, 77, 78, 64, 64, 3, 1, 1)
 W64 = (2, 33, 64, 128, 128, 3, 1, 1)
 W65 = (2, 33, 65, 128, 128, 3, 1, 1)
