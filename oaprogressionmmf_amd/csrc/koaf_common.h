@@ -30,6 +30,9 @@ static inline int koaf_check_launch(const char* what) {
     return KOAF_OK;
 }
 
+// the launch record (koaf.h koaf_launch_log): grid = the tiles, launched = the grid that goes out (koaf_gemm.hip)
+void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);
+
 // the `void* stream` argument of every entry point
 #define STREAM ((hipStream_t)stream)
 

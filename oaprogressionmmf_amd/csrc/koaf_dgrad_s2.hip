@@ -6,10 +6,8 @@
 // and row m is stored at input pixel (n, 2 yy + py, 2 xx + px).  fp16 scheme only (KoafGemm.fmt 1: two pieces per value, three MFMAs per
 // product), the weights from the class's taps of the D plane image [2][Cin][KH KW Cout].
 // The generic kernel runs each class on 128 x 128 tiles with one k-tile in flight and two block barriers per k-step, and its row map sends
-// every tile down the one-row-at-a-time epilogue loop.  Here fwd_s2_kernel's schedule (koaf_fwd_s2.hip, itself wgrad1_kernel::step's): a
-// block of 512 threads (waves 4 x 2) owns a 256 x 256 tile (256 x 128 where Cin is no multiple of 256), two LDS stages hold both operands,
-// one barrier per k-step; register units are refilled two k-tiles ahead and pinned behind the MFMA groups.  Every wave executes every
-// barrier; there is no role split, no spin-wait and no hand-off between blocks.
+// every tile down the one-row-at-a-time epilogue loop.  Here the schedule of koaf_tile256.h on 256 x 256 tiles (256 x 128 where Cin is no
+// multiple of 256), one tile per block.
 // A, two loaders:
 //   AM 0 (3x3): the activation plane images [2][pixels][Cout] of dy (koaf_act_planes: the BatchNorm-backward apply is in the image), 16-B
 //     chunks through registers; a k-tile lies inside one tap (Cout % 32 == 0) and a thread owns the same two rows for a whole tile, their
@@ -26,7 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "koaf.h"
-#include "koaf_pieces.h"
+#include "koaf_tile256.h"
 
 namespace {
 struct Ds2Params {
@@ -56,53 +54,32 @@ struct Ds2Params {
     int part_row0;
 };
 
-constexpr int DS2_NT = 512;
-constexpr int DS2_BM = 256;
-
-// position of a k-tile in the (tap, co) order (block-uniform); past the last tile it wraps to k = 0
-struct Ds2Walk {
-    int kh, kw, coff;
-    __device__ __forceinline__ void next(int C, int nkh, int nkw) {
-        coff += BK;
-        if (coff >= C) {
-            coff = 0;
-            if (++kw == nkw) { kw = 0; ++kh; }
-            if (kh == nkh) kh = 0;
-        }
-    }
-};
-
 // a block-uniform value, pinned to scalar registers
 __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v);
 }
 
 template <int BN, int AM>
-__global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
-    constexpr int BM = DS2_BM, WGN = 2;                                   // waves 4 (M) x 2 (N)
+__global__ void __launch_bounds__(T256_NT) dgrad_s2_kernel(const Ds2Params p) {
+    constexpr int BM = T256_BM, WGN = 2;                                  // waves 4 (M) x 2 (N)
     constexpr int WM = BM / 4, WN = BN / WGN, TM = WM / 32, TN = WN / 32;
-    constexpr int A_PL = plane_dwords(BM, true), B_PL = BN * 16;
-    constexpr int A_ELEMS = 2 * A_PL, B_ELEMS = 2 * B_PL, STAGE = A_ELEMS + B_ELEMS;
+    typedef T256FragRow<BM, BN> Frag;
+    constexpr int A_PL = Frag::A_PL, A_ELEMS = 2 * A_PL, B_ELEMS = 2 * Frag::B_PL, STAGE = A_ELEMS + B_ELEMS;
     constexpr int LDC_S = BN + 4;                                         // epilogue staging row (floats)
     constexpr int HPS = BN == 128 ? 2 : 1;                                // 128-row halves staged at a time (128 columns: both)
     constexpr int SMEM = 2 * STAGE > 128 * HPS * LDC_S ? 2 * STAGE : 128 * HPS * LDC_S;
     static_assert(SMEM * 4 <= 159 * 1024, "two stages of both operands, or the staged tile, in LDS");
     __shared__ __attribute__((aligned(16))) unsigned smem[SMEM];
 
-    // block -> tile: koaf_gemm_kernel's XCD remap (XCD x works through one contiguous chunk of the tile order, column tiles fastest)
+    // block -> tile, column tiles fastest
     const int ntn = p.N / BN;
-    int tm, tn;
-    {
-        const unsigned ntx = gridDim.x, v = blockIdx.x;
-        const unsigned q = ntx >> 3, rem = ntx & 7, x = v & 7, j = v >> 3;
-        const unsigned b = x * q + (x < rem ? x : rem) + j;
-        tn = (int)(b % (unsigned)ntn);
-        tm = (int)(b / (unsigned)ntn);
-    }
+    const unsigned b = t256_xcd_slot(gridDim.x, blockIdx.x);
+    const int tn = (int)(b % (unsigned)ntn), tm = (int)(b / (unsigned)ntn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int nstep = p.K / BK;
 
     const float sca = scale_of_amax(*p.a_amax), scb = scale_of_amax(*p.w_amax);
+    // (alpha and the diverged-operand count stay in the unit: as a shared function they move the kernels' prologue)
     float alpha = p.alpha / (sca * scb);
     if (!koaf_bits_finite(koaf_absbits(*p.a_amax)) || !koaf_bits_finite(koaf_absbits(*p.w_amax))) {
         alpha = __uint_as_float(0x7fc00000u);          // (a diverged operand: the whole output is NaN, as koaf_gemm does)
@@ -137,7 +114,7 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
     // AM 2: the coefficients of the k-tile being converted (one set: the next tile's are fetched behind the tile's last A unit and
     // have the B units' MFMA groups and the barrier to land)
     [[maybe_unused]] v4f na = {0.f, 0.f, 0.f, 0.f}, nb = na, nc = na;
-    auto issue_a = [&](int u, const Ds2Walk& wk) {
+    auto issue_a = [&](int u, const TapWalk& wk) {
         if constexpr (AM == 0) {
             const int j = u >> 1, q = u & 1;
             const int sy = iy0[j] - wk.kh, sx = ix0[j] - wk.kw;
@@ -153,29 +130,21 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
             if constexpr (AM == 2) rc[u] = *(const v4f*)(p.c + ub + avoff);
         }
     };
-    // unit u of the k-tile in registers into the A image at S (AM 1 | 2: TileLoader::finish_unit's arithmetic + split2h)
+    // unit u of the k-tile in registers into the A image at S
     auto store_a = [&](int u, unsigned* S) {
         if constexpr (AM == 0) {
             *(v4i*)&S[(u & 1) * A_PL + (pr + 128u * (u >> 1)) * 20u + 4u * ck] = rp[u];
         } else {
-            constexpr float HMAX = 65504.f;
             v4f v;
+            if constexpr (AM == 2) {
+                // (its own copy of t256_finish4<2>'s expression, the coefficients scaled here: through the function the two kernels move)
+                constexpr float HMAX = 65504.f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float x = ra[u][j];
-                if constexpr (AM == 2) {
-                    x = fmaf(na[j] * sca, x, fmaf(-(nc[j] * sca), rc[u][j], nb[j] * sca));
-                    x = __builtin_amdgcn_fmed3f(x, -HMAX, HMAX);
-                } else {
-                    x = __builtin_amdgcn_fmed3f(x * sca, -HMAX, HMAX);
-                }
-                v[j] = x;
-            }
-            unsigned pl[2][2];
-            split2h(v, pl);
-            const unsigned off = (ar + 64u * u) * 20u + 2u * kq;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) *(uint2*)&S[q * A_PL + off] = make_uint2(pl[q][0], pl[q][1]);
+                for (int j = 0; j < 4; ++j)
+                    v[j] = __builtin_amdgcn_fmed3f(fmaf(na[j] * sca, ra[u][j], fmaf(-(nc[j] * sca), rc[u][j], nb[j] * sca)), -HMAX, HMAX);
+            } else
+                v = t256_finish4<0>(ra[u], na, nb, sca);
+            t256_store_kc_unit(S, A_PL, ar + 64u * u, kq, v);
         }
     };
     auto issue_coef = [&](int coff) {
@@ -186,16 +155,15 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
         }
     };
 
-    // ---- B: BN / 64 units per thread and k-tile = 16 B (8 k) of plane u % 2, row (t / 4) + 128 (u / 2) ----
-    constexpr int NUB = BN / 64;
+    // ---- B: row n0 + t / 4 + 128 (u / 2) of plane u % 2, at the walk's tap ----
+    constexpr int NUB = T256PlaneB<BN>::NU;
     const unsigned bvoff = (unsigned)(t >> 2) * (unsigned)p.w_ld + 8u * (unsigned)(t & 3);      // (32 bits: 128 rows of the D image)
     const unsigned bdst = (unsigned)(t >> 2) * 16u + 4u * ((unsigned)(t & 3) ^ ((unsigned)(t >> 4) & 3u));      // (PlaneLoader's swizzle)
-    v4i rb[NUB];
-    auto issue_b = [&](int u, const Ds2Walk& wk) {
+    T256PlaneB<BN> lb;
+    auto issue_b = [&](int u, const TapWalk& wk) {
         const int64_t koff = wk.kh * p.w_tsh + wk.kw * p.w_ts + wk.coff;
-        rb[u] = *(const v4i*)(p.wd + uniform64((uint64_t)((u & 1) * p.w_ps + (int64_t)(n0 + 128 * (u >> 1)) * p.w_ld + koff)) + bvoff);
+        lb.issue(u, p.wd + uniform64((uint64_t)((u & 1) * p.w_ps + (int64_t)(n0 + 128 * (u >> 1)) * p.w_ld + koff)) + bvoff);
     };
-    auto store_b = [&](int u, unsigned* S) { *(v4i*)&S[A_ELEMS + (u & 1) * B_PL + (u >> 1) * (128 * 16) + bdst] = rb[u]; };
 
     v16f acc[TM][TN];
 #pragma unroll
@@ -205,8 +173,8 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    constexpr int NUT = NUA + NUB, NG = 2 * TN;          // units per k-tile; MFMA groups (16-k slice x column tile) per k-step
-    Ds2Walk wi = {0, 0, 0};                              // the k-tile the next issue fetches
+    constexpr int NUT = NUA + NUB;                       // units per k-tile
+    TapWalk wi = {0, 0, 0, 0};                           // the k-tile the next issue fetches
     int ncoff = 0;                                       // AM 2: first channel of the k-tile whose coefficients the next issue fetches
     auto next_coef = [&]() {
         issue_coef(ncoff);
@@ -219,49 +187,15 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
             if (u == NUA - 1) next_coef();
             issue_a(u, wi);
         }
-        else { store_b(u - NUA, S); issue_b(u - NUA, wi); }
+        else { lb.store(u - NUA, S, A_ELEMS, bdst); issue_b(u - NUA, wi); }
     };
-    auto lgkm0_barrier = [&]() {
-        // (the wait is the BUILTIN: hipcc's wait-count pass does not read inline assembly)
-        __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
-        asm volatile("s_barrier" ::: "memory");
-    };
-    // k-step: the MFMAs of the stage at cur -- per accumulator the order of koaf_gemm_kernel's mma(): 16-k slice g, then lo*hi, hi*lo,
-    // hi*hi -- with the units of the next k-tile dealt out behind its MFMA groups
     auto step = [&](int cur) {
         const unsigned* Au = smem + cur * STAGE;
         const unsigned* Bu = Au + A_ELEMS;
         unsigned* Sn = smem + (cur ^ 1) * STAGE;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            v4i ap[TM][2];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) ap[i][q] = frag_load<BM, true>(Au + q * A_PL, wm * WM + 32 * i, g, lane);
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn) {
-                v4i bp[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) bp[q] = frag_load_ps(Bu + q * B_PL, wn * WN + 32 * jn, g, lane);
-                constexpr int PAH[3] = {1, 0, 0}, PBH[3] = {0, 1, 0};
-#pragma unroll
-                for (int term = 0; term < 3; ++term)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ap[i][PAH[term]]),
-                                                                            __builtin_bit_cast(h16x8, bp[PBH[term]]), acc[i][jn], 0, 0, 0);
-                const int grp = g * TN + jn;
-#pragma unroll
-                for (int u = 0; u < NUT; ++u)
-                    if (u * NG / NUT == grp) unit(u, Sn);
-                // (the scheduler keeps each group's MFMAs, vector work and loads where they are written: koaf_fwd_s2.hip)
-                __builtin_amdgcn_sched_barrier(0x104);
-            }
-        }
+        T256_KSTEP(Frag, true, unit(u, Sn));
         wi.next(p.C, p.nkh, p.nkw);
-        // every wave is done reading this stage and has written its part of the next (the loads stay in flight)
-        lgkm0_barrier();
+        t256_lgkm0_barrier();
     };
 
     // ---- prologue: k-tile 0 into stage 0, k-tile 1 into the registers ----
@@ -274,7 +208,7 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
 #pragma unroll
     for (int u = 0; u < NUT; ++u) unit(u, smem);
     wi.next(p.C, p.nkh, p.nkw);
-    lgkm0_barrier();
+    t256_lgkm0_barrier();
 #pragma unroll 1
     for (int s = 0; s < nstep; ++s) step(s & 1);
 
@@ -282,7 +216,7 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
     const int r = lane & 31, h = lane >> 5;
     float* Cs = reinterpret_cast<float*>(smem);      // all waves passed the k-loop's last barrier: the operand stages are dead
     constexpr int C4 = BN / 4;
-    static_assert(DS2_NT / C4 == 8 * HPS, "eight row threads per column vector and staged half");
+    static_assert(T256_NT / C4 == 8 * HPS, "eight row threads per column vector and staged half");
     const int c4 = t % C4, rq = t / C4, rr = rq & 7, hs = rq >> 3;
     const int col = n0 + 4 * c4;
     v4f bv = {0.f, 0.f, 0.f, 0.f};
@@ -381,14 +315,12 @@ __global__ void __launch_bounds__(DS2_NT) dgrad_s2_kernel(const Ds2Params p) {
 
 template <int BN>
 int ds2_launch(const Ds2Params& p, int am, dim3 grid, hipStream_t s) {
-    if (am == 0) hipLaunchKernelGGL((dgrad_s2_kernel<BN, 0>), grid, dim3(DS2_NT), 0, s, p);
-    else if (am == 1) hipLaunchKernelGGL((dgrad_s2_kernel<BN, 1>), grid, dim3(DS2_NT), 0, s, p);
-    else hipLaunchKernelGGL((dgrad_s2_kernel<BN, 2>), grid, dim3(DS2_NT), 0, s, p);
+    if (am == 0) hipLaunchKernelGGL((dgrad_s2_kernel<BN, 0>), grid, dim3(T256_NT), 0, s, p);
+    else if (am == 1) hipLaunchKernelGGL((dgrad_s2_kernel<BN, 1>), grid, dim3(T256_NT), 0, s, p);
+    else hipLaunchKernelGGL((dgrad_s2_kernel<BN, 2>), grid, dim3(T256_NT), 0, s, p);
     return koaf_check_launch("koaf_dgrad_s2");
 }
 }  // namespace
-
-void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
 
 // One parity class of a stride-2 data gradient, described by g as koaf_conv2d_dgrad_bnb builds it (A = dy with gather 2 at stride 1, from
 // plane images or fp32 with tf 0 | 2; B = the class's taps of the D plane image; the row map; BatchNorm-backward mode 2 optional), on
@@ -400,7 +332,7 @@ int koaf_dgrad_s2(const KoafGemm& g, void* stream) {
     const bool pl = A.kind == 2;
     KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && A.gather == 2 && A.amax && A.stride == 1 && B.kind == 2 && B.gather == 0 && B.planes && B.amax &&
                  !B.tf && g.C && g.ldc == g.N && g.splitk <= 1 && g.nb0 * g.nb1 <= 1 && !g.bias && !g.residual && g.cmap && !g.stats &&
-                 !g.out_planes && g.m_base == 0 && g.M % DS2_BM == 0 && g.N % 128 == 0 && A.C % BK == 0 && A.KH > 0 && A.KW > 0 &&
+                 !g.out_planes && g.m_base == 0 && g.M % T256_BM == 0 && g.N % 128 == 0 && A.C % BK == 0 && A.KH > 0 && A.KW > 0 &&
                  g.K == A.KH * A.KW * A.C && (A.CS == 0 || A.CS == A.C),
                  "koaf_dgrad_s2: bad args");
     KOAF_REQUIRE(pl ? (A.planes && A.zeros && !A.tf) : (A.kind == 0 && A.ptr && (A.tf == 0 || (A.tf == 2 && A.ptr2 && A.sc && A.sh && A.sc2))),
@@ -432,14 +364,13 @@ int koaf_dgrad_s2(const KoafGemm& g, void* stream) {
         p.e_a = 8 / ppi; p.e_b = rem / A.PW; p.e_c = rem % A.PW;
     }
     p.part_row0 = g.part_row0;
-    const int bn = (g.N % 256) == 0 ? 256 : 128;
-    const dim3 grid((unsigned)((g.M / DS2_BM) * (g.N / bn)));
-    KoafGemm rec = g;
-    rec.bm = DS2_BM; rec.bn = bn;
-    koaf_log_launch("koaf_dgrad_s2", rec, grid, grid);
+    const int bn = t256_bn(g.N);
+    const dim3 grid((unsigned)((g.M / T256_BM) * (g.N / bn)));
+    t256_log_launch("koaf_dgrad_s2", g, T256_BM, bn, grid, grid);
     if (!pl) {
+        KoafGemm rec = g;
         rec.K = 0;
-        for (int i = 0; i < 3; ++i) koaf_log_launch("koaf_dgrad_s2", rec, grid, grid);
+        for (int i = 0; i < 3; ++i) t256_log_launch("koaf_dgrad_s2", rec, T256_BM, bn, grid, grid);
     }
     hipStream_t s = (hipStream_t)stream;
     const int am = pl ? 0 : (A.tf == 2 ? 2 : 1);

@@ -16,9 +16,6 @@ constexpr int KOAF_NO_KERNEL = -1000;
 // part_rows: row tiles of the call (koaf_gemm_part_rows); halo / t2d: the 3x3 plane-image kernels M_PH / M_PT; stream: M_KS
 struct TilePlan { int bm, bn; bool vec; int part_rows; bool halo; bool t2d; bool stream; };
 
-// the launch record (koaf.h koaf_launch_log): grid = the tiles, launched = the grid that goes out
-void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);
-
 int koaf_launch_stream(const KoafGemm& g, const TilePlan& tp, dim3 grid, hipStream_t s);
 int koaf_launch_wplanes_act0(const KoafGemm& g, const TilePlan& tp, dim3 grid, hipStream_t s);
 int koaf_launch_wplanes_act1(const KoafGemm& g, const TilePlan& tp, dim3 grid, hipStream_t s);

@@ -4,17 +4,9 @@
 // with both operands K-major fp32 in HBM and the transforms of koaf_gemm's loaders formed on load: dc = dy, or the BatchNorm-backward
 // apply k0 dz + k3 - k2 c of two sources (KoafOperand.tf 2); x~ = x, or relu(in_sc x + in_sh) (tf 1).  fp16 scheme only
 // (KoafGemm.fmt 1: two fp16 pieces per value, three MFMAs per product).
-// The generic kernel (koaf_gemm_kernel, M_KM x M_KM) runs these calls on 128 x 128 tiles with ONE LDS image per operand and two
-// block barriers per 32-pixel k-step: the apply / prologue, the piece split and the LDS store sit between the barriers with the
-// matrix pipe idle, and every element of an operand is converted once per tile of the OTHER dimension.  Here a block of 512 threads
-// (waves 4 x 2) owns a 256 x 256 tile (256 x 128 / 128 x 256 where a dimension is 128 wide) -- half the conversions and half the L2
-// reads per operand element -- with two LDS stages per operand and one barrier per k-step:
-//     step s:  MFMAs of k-tile s (stage s % 2)  ||  convert + split + store of k-tile s + 1 (registers -> stage (s + 1) % 2),
-//              each register unit refilled with its loads of k-tile s + 2 as soon as it is converted
-// so a load has a whole k-step to land and the vector work runs in the shadow of the matrix instructions (its own wave's and
-// those of the second wave on the SIMD).  Register slots are static (one k-tile in registers, unit by unit); the loads behind the
-// end of the k-range are issued unconditionally, clamped into the tensor, into registers whose conversion nobody reads.
-// Every wave executes every barrier; there is no role split, no spin-wait and no hand-off between blocks.
+// The generic kernel (koaf_gemm_kernel, M_KM x M_KM) runs these calls on 128 x 128 tiles, and every element of an operand is converted
+// once per tile of the OTHER dimension.  Here the schedule of koaf_tile256.h, where it began, on 256 x 256 tiles (256 x 128 / 128 x 256
+// where a dimension is 128 wide); the loads behind the end of the k-range are clamped into the tensor.
 // Arithmetic, pieces, LDS images (plane[k][ROWS + 32 pad], koaf_pieces.h) and the order of the piece products per accumulator and
 // 16-k slice are those of TileLoader + koaf_gemm_kernel's mma(): slabs and dw are bit-identical to the generic path
 // (tests/test_wgrad1x1_gpu.py).  Split-K plan, slab layout and the XCD remap are koaf_gemm's.
@@ -28,7 +20,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "koaf.h"
-#include "koaf_pieces.h"
+#include "koaf_tile256.h"
 
 namespace {
 struct Wg1Params {
@@ -49,8 +41,6 @@ struct Wg1Params {
     int H, W, C, PH, PW, KW, stride, pad, pad_w;
 };
 
-constexpr int WG1_NT = 512;
-
 constexpr int WG1_TAB = 4 * BK;          // gathered B: ring of four table rows (k-tiles s + 1 .. s + 3 are live during step s)
 constexpr unsigned WG1_INVALID = 0x80000000u;
 
@@ -60,7 +50,7 @@ template <int R, int TF, bool G = false>
 struct Wg1Loader {
     static constexpr int NU = R / 64;                 // units per thread and k-tile
     static constexpr int CV = R / 4;                  // threads across a k-row
-    static constexpr int RP = WG1_NT / CV;            // k-rows per pass of the block
+    static constexpr int RP = T256_NT / CV;            // k-rows per pass of the block
     static constexpr int SK = R / 2 + 16;             // dwords per k-row of a plane image
     static constexpr int PL = plane_dwords(R, false);
     v4f r[NU];
@@ -109,6 +99,7 @@ struct Wg1Loader {
     // rows lie inside the k-range (G: validity is the unit's bit, border taps included; there is no FULL form)
     template <bool FULL>
     __device__ __forceinline__ void convert(int i, int klim, unsigned* S) {
+        // (its own copy of t256_finish4's expressions: through the function hipcc commutes the TF 0 products of twelve kernels here)
         constexpr float HMAX = 65504.f;
         const bool ok = G ? ((vm >> i) & 1u) == 0u : (FULL || (int)(kr + (unsigned)(RP * i)) < klim);
         v4f v;
@@ -135,11 +126,12 @@ struct Wg1Loader {
 };
 
 template <int BM, int BN, int TFA, int TFB, bool GB>
-__global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
+__global__ void __launch_bounds__(T256_NT) wgrad1_kernel(const Wg1Params p) {
     constexpr int WGM = 4, WGN = 2;                                   // waves along M x N
     constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 32, TN = WN / 32;
     typedef Wg1Loader<BM, TFA> LA;
     typedef Wg1Loader<BN, TFB, GB> LB;
+    typedef T256FragKM<BM, BN> Frag;
     constexpr int A_ELEMS = 2 * LA::PL, B_ELEMS = 2 * LB::PL, STAGE = A_ELEMS + B_ELEMS;
     static_assert((2 * STAGE + WG1_TAB) * 4 <= 160 * 1024, "two stages of both operands in LDS");
     __shared__ __attribute__((aligned(16))) unsigned smem[2 * STAGE + (GB ? WG1_TAB : 0)];
@@ -163,6 +155,7 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
     const int klen = max(kend - kbeg, 0), nstep = (klen + BK - 1) / BK;
 
     const float sca = scale_of_amax(*p.a_amax), scb = p.b_scale;
+    // (alpha and the diverged-operand count stay in the unit: as a shared function they move the kernels' prologue)
     float alpha = 1.f / (sca * scb);
     if (!koaf_bits_finite(koaf_absbits(*p.a_amax))) {
         alpha = __uint_as_float(0x7fc00000u);          // (a diverged dy: the whole gradient is NaN, as koaf_gemm does)
@@ -202,8 +195,8 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     // conversion unit u of the k-tile in registers (A units first) into the stage at S, then the unit's loads of the k-tile at k2
-    constexpr int NUT = LA::NU + LB::NU, NG = 2 * TN;                 // units per k-tile; MFMA groups (16-k slice x column tile) per k-step
-    auto unit = [&](auto full, int u, int klim, unsigned* S, int k2) {
+    constexpr int NUT = LA::NU + LB::NU;                              // units per k-tile
+    auto unit = [&](int u, auto full, int klim, unsigned* S, int k2) {
         constexpr bool FULL = decltype(full)::value;
         if (u < LA::NU) {
             la.template convert<FULL>(u, klim, S);
@@ -214,8 +207,8 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             else lb.issue(u - LA::NU, k2, p.K);
         }
     };
-    // k-step: the MFMAs of the stage at cur -- per accumulator the order of koaf_gemm_kernel's mma(): 16-k slice g, then lo*hi, hi*lo,
-    // hi*hi -- with the units of the next k-tile dealt out behind its MFMA groups
+    // (this unit keeps the inline-assembly wait it was tuned with; the other three take the builtin, t256_lgkm0_barrier)
+    auto lgkm0_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     auto step = [&](auto full, int cur, int klim, int k2) {
         const unsigned* Au = smem + cur * STAGE;
         const unsigned* Bu = Au + A_ELEMS;
@@ -224,42 +217,14 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             // the table row of the k-tile after k2: its readers pass this step's barrier first; the row it replaces was last read three steps ago
             if (threadIdx.x < BK) table((k2 - kbeg) / BK + 1, threadIdx.x);
         }
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            v4i ap[TM][2];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) ap[i][q] = frag_load<BM, false>(Au + q * LA::PL, wm * WM + 32 * i, g, lane);
-#pragma unroll
-            for (int jn = 0; jn < TN; ++jn) {
-                v4i bp[2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) bp[q] = frag_load<BN, false>(Bu + q * LB::PL, wn * WN + 32 * jn, g, lane);
-                constexpr int PAH[3] = {1, 0, 0}, PBH[3] = {0, 1, 0};
-#pragma unroll
-                for (int term = 0; term < 3; ++term)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8, ap[i][PAH[term]]),
-                                                                            __builtin_bit_cast(h16x8, bp[PBH[term]]), acc[i][jn], 0, 0, 0);
-                const int grp = g * TN + jn;
-#pragma unroll
-                for (int u = 0; u < NUT; ++u)
-                    if (u * NG / NUT == grp) unit(full, u, klim, Sn, k2);
-                // the scheduler keeps each group's MFMAs, vector work and loads where they are written (only fragment reads and scalar
-                // work may cross): left free, it sinks every global load to the end of the step, in front of its first use
-                __builtin_amdgcn_sched_barrier(0x104);
-            }
-        }
-        // every wave is done reading this stage and has written its part of the next (the loads stay in flight)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        T256_KSTEP(Frag, true, unit(u, full, klim, Sn, k2));
+        lgkm0_barrier();
     };
 
     if (nstep > 0) {
         if constexpr (GB) {
             if (threadIdx.x < 3 * BK) table(threadIdx.x / BK, threadIdx.x % BK);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            lgkm0_barrier();
         }
 #pragma unroll
         for (int i = 0; i < LA::NU; ++i) la.issue(i, kbeg, p.K);
@@ -269,8 +234,8 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
             else lb.issue(i, kbeg, p.K);
         }
 #pragma unroll
-        for (int u = 0; u < NUT; ++u) unit(std::false_type{}, u, klen, smem, kbeg + BK);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        for (int u = 0; u < NUT; ++u) unit(u, std::false_type{}, klen, smem, kbeg + BK);
+        lgkm0_barrier();
     }
     // steps whose NEXT k-tile lies wholly inside the range convert without zero fill
     const int nfull = max(klen / BK - 1, 0);
@@ -300,7 +265,7 @@ __global__ void __launch_bounds__(WG1_NT) wgrad1_kernel(const Wg1Params p) {
 
 template <int BM, int BN, bool GB>
 int wg1_launch(const Wg1Params& p, int tfa, int tfb, dim3 grid, hipStream_t s) {
-#define WG1_GO(TA, TB) hipLaunchKernelGGL((wgrad1_kernel<BM, BN, TA, TB, GB>), grid, dim3(WG1_NT), 0, s, p)
+#define WG1_GO(TA, TB) hipLaunchKernelGGL((wgrad1_kernel<BM, BN, TA, TB, GB>), grid, dim3(T256_NT), 0, s, p)
     if (tfa == 2) { if (tfb) WG1_GO(2, 1); else WG1_GO(2, 0); }
     else { if (tfb) WG1_GO(0, 1); else WG1_GO(0, 0); }
 #undef WG1_GO
@@ -313,8 +278,6 @@ int wg1_tile(const Wg1Params& p, int bm, int bn, int tfa, int tfb, dim3 grid, hi
     return wg1_launch<128, 256, GB>(p, tfa, tfb, grid, s);
 }
 }  // namespace
-
-void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
 
 // the weight gradient described by g (koaf_conv2d_wgrad's descriptor: A = dy [K][M] K-major with tf 0 | 2, B = x with tf 0 | 1 -- [K][N]
 // K-major for 1x1 / stride 1, or gather 1 over the NHWC tensor for stride 2 --, fmt 1, act16 0, C = slabs or dw) on bm x bn tiles; the
@@ -343,9 +306,7 @@ int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream) {
     p.M = g.M; p.N = g.N; p.K = g.K; p.splitk = g.splitk;
     p.H = B.H; p.W = B.W; p.C = B.C; p.PH = B.PH; p.PW = B.PW; p.KW = B.KW; p.stride = B.stride; p.pad = B.pad; p.pad_w = B.pad_w;
     const dim3 grid((unsigned)((g.M / bm) * (g.N / bn)), (unsigned)g.splitk);
-    KoafGemm rec = g;
-    rec.bm = bm; rec.bn = bn;
-    koaf_log_launch("koaf_wgrad1", rec, grid, grid);
+    t256_log_launch("koaf_wgrad1", g, bm, bn, grid, grid);
     hipStream_t s = (hipStream_t)stream;
     return gb ? wg1_tile<true>(p, bm, bn, g.A.tf, B.tf, grid, s) : wg1_tile<false>(p, bm, bn, g.A.tf, B.tf, grid, s);
 }

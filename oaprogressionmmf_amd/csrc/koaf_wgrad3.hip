@@ -201,8 +201,6 @@ __global__ void __launch_bounds__(768) wgrad3x3_ring_kernel(Wg3Params p) {
 }
 }  // namespace
 
-void koaf_log_launch(const char* variant, const KoafGemm& g, dim3 grid, dim3 launched);      // koaf_gemm.hip
-
 // k-ranges of the ring kernel for this layer: about four rounds of one block per CU (the weight gradients run on a low-priority
 // stream beside the critical path: blocks of ~0.5 ms give the CUs back often enough; 256 long blocks cost 15 ms per step), whole
 // multiples of 8 (an XCD each)

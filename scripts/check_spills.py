@@ -2,8 +2,8 @@
 (csrc/koaf_gemm*.hip, with the Makefile's own flags) with -Rpass-analysis=kernel-resource-usage (1 min) and prints VGPRs / spilled VGPRs / scratch per instantiation that spills, against the
 counts recorded when the round-4 regression was fixed (a 64-bit row index in the shared epilogue had cost every kernel ~30 VGPRs and
 the persistent 1x1 kernels 40-90 spilled registers: +40 ms per step, invisible in the build output).
-The one-pass optimizer / BCE kernels (koaf_optim.hip, koaf_bce.hip) and the 256-wide-tile 1x1 weight-gradient kernels (koaf_wgrad1.hip)
-are listed too and must not spill at all.
+The one-pass optimizer / BCE kernels (koaf_optim.hip, koaf_bce.hip) and the kernels on the 256-row tile schedule of koaf_tile256.h
+(koaf_wgrad1.hip, koaf_fwd_s2.hip, koaf_dgrad_s2.hip, koaf_fwd1.hip) are listed too and must not spill at all.
     python scripts/check_spills.py"""
 import re, sys
 from pathlib import Path

@@ -462,7 +462,8 @@ def test_clock_per_kernel_reduction(tmp_path):
 
 def test_makefile_compiles_every_unit_once_with_the_matrix_pipe_flag():
     """Every csrc/*.hip except the stamps unit goes into libkoaf.so exactly once, and every unit that receives the GEMM's
-    matrix-pipe code (koaf_gemm_kernel.h, directly or through another header; the attention kernel; the plane cutters) is built
+    matrix-pipe code (koaf_gemm_kernel.h or the 256-row tile schedule koaf_tile256.h, directly or through another header; the attention
+    kernel; the plane cutters) is built
     with -amdgpu-mfma-vgpr-form: a unit that misses the flag compiles, passes every numerical test and is slower."""
     import re
     import shlex
@@ -483,8 +484,9 @@ def test_makefile_compiles_every_unit_once_with_the_matrix_pipe_flag():
                 headers(csrc / h, seen)
         return seen
 
-    needs = [n for n in want if "koaf_gemm_kernel.h" in headers(csrc / n, set()) or n in ("koaf_attention.hip", "koaf_planes.hip")]
-    assert len(needs) >= 5 and "koaf_gemm.hip" in needs
+    needs = [n for n in want if {"koaf_gemm_kernel.h", "koaf_tile256.h"} & headers(csrc / n, set()) or n in ("koaf_attention.hip", "koaf_planes.hip")]
+    assert len(needs) >= 9 and "koaf_gemm.hip" in needs
+    assert {"koaf_wgrad1.hip", "koaf_fwd_s2.hip", "koaf_dgrad_s2.hip", "koaf_fwd1.hip"} <= set(needs)
     for a in lines:
         if a[a.index("-c") + 1] in needs:
             assert "-amdgpu-mfma-vgpr-form" in a and a[a.index("-amdgpu-mfma-vgpr-form") - 1] == "-mllvm", a
