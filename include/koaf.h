@@ -283,7 +283,9 @@ typedef struct KoafBnApply {
  * Activation arguments per entry point: koaf_conv2d_fwd / koaf_gconv3x3_fwd x, y; koaf_conv2d_dgrad(_bnb) dy_apply->c and
  * bnb->c / y / c2; koaf_conv2d_wgrad / koaf_gconv3x3_wgrad x and dy_apply->c; koaf_stem_fwd y; koaf_stem_wgrad / koaf_stem_dgrad dy_apply->c; koaf_colstats x; koaf_bn_add_relu /
  * koaf_bn_relu c, idt, y; koaf_bn_bwd_reduce c, ymask; koaf_bn_bwd_apply c; koaf_maxpool_fwd c, y; koaf_gap_fwd y; koaf_act_planes
- * x (tf 0 / 1) or x2 (tf 2). */
+ * x (tf 0 / 1) or x2 (tf 2).  The activation arguments of ONE call share one storage: the entry points cannot tell (every pointer is
+ * a float*), a caller that mixed them would have a two-byte tensor read four bytes per element, past its end -- the Python
+ * wrappers refuse such a call before anything is launched (ops/_base.py _act16). */
 
 /* ---- Convolution (nn.Conv2d, bias-free; _torchvision.py:23-31) as implicit GEMM on NHWC -------
  * x [N,H,W,Cin], w packed [Cout,KH,KW,Cin] (the memory of a channels_last (Cout,Cin,KH,KW)
@@ -530,7 +532,9 @@ int koaf_window_minmax(const int64_t* table, int32_t dtype, int32_t B, int32_t R
 int koaf_input_pipeline(const int64_t* table, int32_t dtype, float* y, const float* mm, const float* params, int32_t B, int32_t R,
                         int32_t C, int32_t S, int32_t pool, int32_t pool_s, int32_t layout, float mean, float stdv, void* stream);
 
-/* ---- MaxPool2d 3x3 s2 p1 over relu(sc*c+sh) (_torchvision.py:173-174), GAP (:182) ------------ */
+/* ---- MaxPool2d 3x3 s2 p1 over relu(sc*c+sh) (_torchvision.py:173-174), GAP (:182) ------------
+ * A NaN pre-activation stays a NaN (as in koaf_bn_add_relu) and takes its windows (as in F.max_pool2d; argmax = its last position
+ * in the window), so it reaches y and status word 0 instead of turning into a zero. */
 int koaf_maxpool_fwd(const float* c, const float* sc, const float* sh, float* y, uint8_t* argmax,
                      int32_t N, int32_t H, int32_t W, int32_t C, int32_t act16, void* stream);
 /* da [N,H,W,C] (gradient wrt relu(bn(c))) gathered from dy via argmax (every element written) */

@@ -566,8 +566,11 @@ __global__ void __launch_bounds__(256) maxpool_fwd_kernel(const float* __restric
                 v4f v = load4<B16>(c, ((int64_t)(n * H + iy) * W + ix) * C + cv);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float a = fmaxf(v[j] * s4[j] + h4[j], 0.f);
-                    if (a > best[j]) { best[j] = a; bi[j] = kh * 3 + kw; }
+                    // (a NaN stays a NaN, as in bn_add_relu_kernel -- fmaxf alone would return the 0 -- and takes the window, as in
+                    // F.max_pool2d: it is counted below and reaches the consumers instead of turning into a healthy zero)
+                    const float z = v[j] * s4[j] + h4[j];
+                    const float a = z != z ? z : fmaxf(z, 0.f);
+                    if (a > best[j] || a != a) { best[j] = a; bi[j] = kh * 3 + kw; }
                 }
             }
         }

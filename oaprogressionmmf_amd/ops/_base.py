@@ -50,6 +50,31 @@ def _a16(t):
     return 1 if (t is not None and t.dtype == torch.bfloat16) else 0
 
 
+def _act16(what, **acts):
+    """the `act16` argument of a call whose activation tensors are `acts` (name=tensor or None): all of them fp32, or all of them
+    bf16.  The entry points take every pointer as float* and read all of a call's activations at the one width act16 names, so a
+    call that mixes the two storages would read (or write) a two-byte tensor four bytes per element, past its end: refused here,
+    naming the call and the argument, before anything is launched"""
+    first = dt = None
+    for name, t in acts.items():
+        if t is None:
+            continue
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise KoafError(f"{what}: {name} is an fp32 or bf16 activation tensor, got {t.dtype}")
+        if dt is None:
+            first, dt = name, t.dtype
+        elif t.dtype != dt:
+            raise KoafError(f"{what}: {name} is {t.dtype} but {first} is {dt}: the activations of one call share one storage")
+    return 1 if dt == torch.bfloat16 else 0
+
+
+def _grads32(what, **grads):
+    """gradients are never stored as bf16 (koaf.h): refuse a gradient argument (name=tensor or None) that is not fp32"""
+    for name, t in grads.items():
+        if t is not None and t.dtype != torch.float32:
+            raise KoafError(f"{what}: {name} is an fp32 gradient tensor, got {t.dtype}")
+
+
 def _stream():
     if _STATUS is None or _STATUS_DEV != torch.cuda.current_device():
         _status_buffer()

@@ -4,7 +4,7 @@ import ctypes
 import torch
 
 from .._lib import KoafBnApply, KoafError, check, lib
-from ._base import _a16, _empty, _i32, _ptr, _stream, conv_out
+from ._base import _act16, _empty, _grads32, _i32, _ptr, _stream, conv_out
 
 
 class BnApply(object):
@@ -26,10 +26,12 @@ class BnApply(object):
         return (self.dz, self.c, self.coef, self.amax, self._koaf_planes, getattr(self.c, "_koaf_xplanes", None))
 
     def materialize(self, out=None, want_amax=False):
+        act16 = _act16("bn_bwd_apply", c=self.c)
+        _grads32("bn_bwd_apply", dz=self.dz, out=out)
         dc = out if out is not None else torch.empty(self.c.shape, device=self.c.device, dtype=torch.float32)
         amax = torch.zeros(1, device=self.c.device, dtype=torch.float32) if want_amax else None
         check(lib().koaf_bn_bwd_apply(_ptr(self.dz), _ptr(self.c), _ptr(self.mean), _ptr(self.coef), _ptr(dc), self.rows, self.C,
-                                      _ptr(amax), _a16(self.c), _stream()), "bn_bwd_apply")
+                                      _ptr(amax), act16, _stream()), "bn_bwd_apply")
         if want_amax:
             dc._koaf_amax = amax
         return dc
@@ -53,9 +55,10 @@ def _colpart_rows(rows, C, what):
 
 def colstats(x, rows, C, shift=None):
     L = lib()
+    act16 = _act16("colstats", x=x)
     part = _empty((_colpart_rows(rows, C, "colstats"), 2, C), x)      # (fp32 whatever the storage type of x)
     r = _i32(0)
-    check(L.koaf_colstats(_ptr(x), rows, C, _ptr(part), ctypes.addressof(r), _ptr(shift), _a16(x), _stream()), "colstats")
+    check(L.koaf_colstats(_ptr(x), rows, C, _ptr(part), ctypes.addressof(r), _ptr(shift), act16, _stream()), "colstats")
     return part
 
 
@@ -79,10 +82,11 @@ def bn_finalize(part, C, count, gamma, beta, running_mean, running_var, nbt, mom
 
 
 def bn_add_relu(c, saved, rows, C, idt=None, idsaved=None, out=None):
+    act16 = _act16("bn_add_relu", c=c, idt=idt, out=out)
     y = out if out is not None else torch.empty_like(c)
     check(lib().koaf_bn_add_relu(_ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(idt),
                                  _ptr(idsaved[2]) if idsaved is not None else None,
-                                 _ptr(idsaved[3]) if idsaved is not None else None, _ptr(y), rows, C, _a16(c), _stream()),
+                                 _ptr(idsaved[3]) if idsaved is not None else None, _ptr(y), rows, C, act16, _stream()),
           "bn_add_relu")
     return y
 
@@ -95,6 +99,8 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
     train=False: the BatchNorm ran on its running statistics (`saved` holds them), so dc = sc*dz (koaf_bn_bwd_finalize_eval);
     dgamma / dbeta may be None (frozen parameters): they are then not written."""
     L = lib()
+    act16 = _act16("bn_bwd", c=c, ymask=ymask)
+    _grads32("bn_bwd", g=g, dz_out=dz_out, dc_out=dc_out, **({} if pool is None else {"pool[0]": pool[0]}))
     if pool is not None:
         # g is the gradient of the max-pool behind this BatchNorm(+ReLU): pool = (pool_g [N,OH,OW,C], argmax, N, H, W); the pool's
         # input gradient is gathered by the reduction itself (koaf_bn_bwd_reduce_pool) and only the masked dz is written
@@ -105,7 +111,7 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
         r = _i32(0)
         dzmax = _empty((1,), pg) if fused else None
         check(L.koaf_bn_bwd_reduce_pool(_ptr(pg), _ptr(am), _ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(saved[0]), _ptr(saved[1]),
-                                        _ptr(dz), _ptr(part), ctypes.addressof(r), pN, pH, pW, C, _ptr(dzmax), _a16(c), _stream()),
+                                        _ptr(dz), _ptr(part), ctypes.addressof(r), pN, pH, pW, C, _ptr(dzmax), act16, _stream()),
               "bn_bwd_reduce_pool")
         return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
     if mask_mode != 0 and dz_out is None:
@@ -115,7 +121,7 @@ def bn_bwd(g, c, saved, rows, C, count, dgamma, dbeta, mask_mode, ymask=None, dz
     dzmax = _empty((1,), g) if fused else None
     check(L.koaf_bn_bwd_reduce(_ptr(g), _ptr(c), _ptr(ymask), _ptr(saved[2]), _ptr(saved[3]), _ptr(saved[0]),
                                _ptr(saved[1]), mask_mode, _ptr(dz_out), _ptr(part), ctypes.addressof(r), rows, C,
-                               _ptr(dzmax), _a16(c), _stream()), "bn_bwd_reduce")
+                               _ptr(dzmax), act16, _stream()), "bn_bwd_reduce")
     dz = dz_out if dz_out is not None else g
     return _bn_bwd_tail(part[:r.value], 2, 1, dz, c, saved, rows, C, count, dgamma, dbeta, dc_out, fused, dzmax, train)
 
@@ -138,7 +144,7 @@ def _bn_bwd_tail(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta, dc
     if fused:
         return BnApply(dz, c, coef, amax, saved[0], rows, C)
     dc = dc_out if dc_out is not None else torch.empty(c.shape, device=c.device, dtype=torch.float32)
-    check(L.koaf_bn_bwd_apply(_ptr(dz), _ptr(c), _ptr(saved[0]), _ptr(coef), _ptr(dc), rows, C, None, _a16(c), _stream()),
+    check(L.koaf_bn_bwd_apply(_ptr(dz), _ptr(c), _ptr(saved[0]), _ptr(coef), _ptr(dc), rows, C, None, _act16("bn_bwd_apply", c=c), _stream()),
           "bn_bwd_apply")
     return dc
 
@@ -153,9 +159,10 @@ def bn_bwd_from_part(part, nsum, i1, dz, c, saved, rows, C, count, dgamma, dbeta
 
 def maxpool_fwd(c, saved, N, H, W, C):
     OH, OW = conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1)
+    act16 = _act16("maxpool_fwd", c=c)
     y = _empty((N, OH, OW, C), c, dtype=c.dtype)
     am = _empty((N, OH, OW, C), c, dtype=torch.uint8)
-    check(lib().koaf_maxpool_fwd(_ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(y), _ptr(am), N, H, W, C, _a16(c), _stream()),
+    check(lib().koaf_maxpool_fwd(_ptr(c), _ptr(saved[2]), _ptr(saved[3]), _ptr(y), _ptr(am), N, H, W, C, act16, _stream()),
           "maxpool_fwd")
     return y, am
 
@@ -167,8 +174,9 @@ def maxpool_bwd(dy, am, N, H, W, C):
 
 
 def gap_fwd(y, N, HW, C):
+    act16 = _act16("gap_fwd", y=y)
     out = _empty((N, C), y)
-    check(lib().koaf_gap_fwd(_ptr(y), _ptr(out), N, HW, C, _a16(y), _stream()), "gap_fwd")
+    check(lib().koaf_gap_fwd(_ptr(y), _ptr(out), N, HW, C, act16, _stream()), "gap_fwd")
     return out
 
 

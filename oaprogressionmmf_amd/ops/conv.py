@@ -6,7 +6,7 @@ import os
 import torch
 
 from .._lib import KoafBnb, KoafEmit, KoafError, KoafGemm, KoafLaunchRec, KoafTail, KoafWImg, KoafWPlane, check, defines, lib
-from ._base import _a16, _empty, _i32, _prof_begin, _prof_end, _ptr, _stream, conv_out
+from ._base import _a16, _act16, _empty, _grads32, _i32, _prof_begin, _prof_end, _ptr, _stream, conv_out
 from .bn import BnApply, _dy_args
 
 # Convolutions run on the fp16 contraction scheme (koaf.h: KoafGemm.fmt 1) whenever their operands' scales are known
@@ -35,9 +35,16 @@ def act_planes(x, npix, C, tf=0, sc=None, sh=None, x2=None, sc2=None, amax=None,
     """fp16 piece planes [2][npix][C] (+ the zero chunk) of x (tf 0), relu(sc*x+sh) (tf 1) or sc*x + sh - sc2*x2 (tf 2), times
     the operand scale (scale(*amax) or fscale): the A operand of the gathered convolution kernels (koaf.h koaf_act_planes)."""
     L = lib()
+    if tf == 2:         # x is the gradient dz (fp32), x2 the conv output c in either storage
+        _grads32("act_planes", x=x)
+        act16 = _act16("act_planes", x2=x2)
+    else:               # x is the activation, in either storage; there is no second source
+        if x2 is not None:
+            raise KoafError(f"act_planes: x2 belongs to tf 2, got it with tf {tf}")
+        act16 = _act16("act_planes", x=x)
     out = torch.empty(L.koaf_act_planes_elems(npix, C), device=x.device, dtype=torch.int16)
     check(L.koaf_act_planes(_ptr(x), _ptr(x2), npix, C, tf, _ptr(sc), _ptr(sh), _ptr(sc2), _ptr(amax), float(fscale),
-                            out.data_ptr(), _a16(x2 if tf == 2 else x), _stream()), "act_planes")
+                            out.data_ptr(), act16, _stream()), "act_planes")
     return out
 
 

@@ -10,7 +10,9 @@ test_kernels_gpu.py compares whole tensors by a ratio of norms; here every eleme
     for results through erff / expf / powf / rsqrt, where no bound can be derived; never below the bar test_kernels_gpu.py
     already holds the kernel to (its norm-ratio bar times max|ref| as a per-element figure).  The figures beside those
     asserts -- kernel error / yardstick error -- were measured on an MI355X; they document, the bar is computed.
-The references are float64 torch / numpy on the CPU fed the same fp32 inputs (elem_refs.py)."""
+The references are float64 torch / numpy on the CPU fed the same fp32 inputs (elem_refs.py).
+The case helpers of koaf_bn.hip's kernels take store=: torch.float32 here; test_elem_edges_bf16_gpu.py runs them again with the
+activations stored as bf16, and holds the activation plane images (koaf_planes.hip) per element in both storages."""
 import math
 import os
 
@@ -76,13 +78,15 @@ def saved_of(mean, invstd, sc, sh, dev):
 WIDTHS = [4, 8, 128, 512, 1024, 2048, 3072]
 
 
-def _colstats_case(ops, dev, rows, C, seed):
+def _colstats_case(ops, dev, rows, C, seed, store=torch.float32):
+    """store: the storage of the activation x (elem_refs.stored: rounded on the CPU, the reference takes the widened values); the
+    partial sums are fp32 in either storage and owe the same bound"""
     g = gen(seed)
-    x = torch.randn(rows, C, generator=g) * 2.0 + torch.randn(C, generator=g)[None, :]
+    x = R.stored(torch.randn(rows, C, generator=g) * 2.0 + torch.randn(C, generator=g)[None, :], store)
     for shift in (None, torch.randn(C, generator=g)):
         lib_rows = ops.lib().koaf_colpart_rows(rows, C)
         assert lib_rows == R.col_geom(rows, C)["nblk"], (rows, C)
-        part = ops.colstats(x.to(dev), rows, C, shift=None if shift is None else shift.to(dev))
+        part = ops.colstats(x.to(store).to(dev), rows, C, shift=None if shift is None else shift.to(dev))
         assert part.shape == (lib_rows, 2, C)
         got = part.double().sum(0).cpu()            # (the second stage is fp64: exact to the last fp32 bit or so; allowed for in m)
         v = x.double() - (0.0 if shift is None else shift.double()[None, :])
@@ -98,15 +102,20 @@ def test_colstats_geometry(dev, C):
         _colstats_case(ops, dev, rows, C, 100 + i)
 
 
-def _bn_bwd_case(ops, dev, rows, C, seed, modes=(0, 1, 2)):
+def _bn_bwd_case(ops, dev, rows, C, seed, modes=(0, 1, 2), store=torch.float32):
+    """store: the storage of the activations c and ymask; gradients, dz, dc and the per-channel vectors are fp32 in either"""
     g = gen(seed)
     sc, sh = torch.randn(C, generator=g) * 0.5 + 1.0, torch.randn(C, generator=g) * 0.3
     mean, invstd = torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) + 0.5
-    c = R.draw_preact(g, (rows, C), sc, sh)
-    y = torch.randn(rows, C, generator=g)           # mask_mode 1 reads the sign of y itself: no arithmetic, nothing borderline
+    c = R.draw_preact(g, (rows, C), sc, sh, store=store)
+    y = R.stored(torch.randn(rows, C, generator=g), store)      # mask_mode 1 reads the sign of y itself: no arithmetic, nothing borderline
+    if store == torch.bfloat16:
+        # the sign test on the widened bf16 value: +0 and -0 are not positive, the smallest positive subnormal (0x0001) is
+        y.view(-1)[:3] = torch.tensor([0.0, -0.0, 2.0 ** -133])
+        assert torch.equal(R.bf16_bits(y.view(-1)[:3].bfloat16()), torch.tensor([0x0000, 0x8000, 0x0001]))
     grad = torch.randn(rows, C, generator=g)
     saved = saved_of(mean, invstd, sc, sh, dev)
-    cd = c.to(dev)
+    cd = c.to(store).to(dev)
     for mode in modes:
         mask = {0: torch.ones(rows, C, dtype=torch.bool), 1: y > 0, 2: (c.double() * sc.double() + sh.double()) > 0}[mode]
         dz_ref = torch.where(mask, grad, torch.zeros(()))
@@ -115,7 +124,7 @@ def _bn_bwd_case(ops, dev, rows, C, seed, modes=(0, 1, 2)):
             gd = grad.to(dev)
             dz_out = torch.full((rows, C), float("nan"), device=dev) if separate else None
             dgm, dbt = torch.empty(C, device=dev), torch.empty(C, device=dev)
-            dc = ops.bn_bwd(gd, cd, saved, rows, C, rows, dgm, dbt, mode, ymask=y.to(dev) if mode == 1 else None, dz_out=dz_out)
+            dc = ops.bn_bwd(gd, cd, saved, rows, C, rows, dgm, dbt, mode, ymask=y.to(store).to(dev) if mode == 1 else None, dz_out=dz_out)
             what = f"bn_bwd {rows}x{C} mode {mode} {'separate' if separate else 'in place'}"
             dz = dz_out if separate else gd
             if mode == 0 and not separate:
@@ -381,27 +390,34 @@ def test_fill_dropout_past_the_grid_cap(dev):
     within(y2c[k2], x2[k2].double() / (1 - p), 2 * U * x2[k2].double() / (1 - p), "dropout2d scaling")
 
 
-def _tail_case(ops, dev, rows, C, seed):
-    """bn_add_relu (plain, + identity, + identity through its own BatchNorm) and bn_bwd_apply, per element"""
+def _tail_case(ops, dev, rows, C, seed, store=torch.float32):
+    """bn_add_relu (plain, + identity, + identity through its own BatchNorm) and bn_bwd_apply, per element.  store: the storage of
+    c, idt and y; y stored as bf16 owes the fp32 bound B plus the rounding of the store, elem_refs.stored16_bound(ref, B)"""
     g = gen(seed)
-    c, idt = torch.randn(rows, C, generator=g), torch.randn(rows, C, generator=g)
+    c, idt = R.stored(torch.randn(rows, C, generator=g), store), R.stored(torch.randn(rows, C, generator=g), store)
+    out_bound = (lambda ref, B: B) if store == torch.float32 else R.stored16_bound
     s3 = torch.stack([torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.5 + 1,
                       torch.randn(C, generator=g) * 0.1])
     sd = torch.stack([torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.5 + 1,
                       torch.randn(C, generator=g) * 0.1])
-    cd, idd, s3d, sdd = c.to(dev), idt.to(dev), s3.to(dev), sd.to(dev)
+    cd, idd, s3d, sdd = c.to(store).to(dev), idt.to(store).to(dev), s3.to(dev), sd.to(dev)
     c64, i64 = c.double(), idt.double()
     p1, h1 = c64 * s3[2].double(), s3[3].double()
     p2, h2 = i64 * sd[2].double(), sd[3].double()
     # relu is 1-Lipschitz: the bound of its argument holds for its result
     # fmaf(c, sc, sh): one rounding (k = 1)
-    within(ops.bn_add_relu(cd, s3d, rows, C), torch.relu(p1 + h1), U * (p1.abs() + h1.abs()), f"bn_add_relu {rows}x{C}")
+    ref = torch.relu(p1 + h1)
+    yk = ops.bn_add_relu(cd, s3d, rows, C)
+    assert yk.dtype == store
+    within(yk, ref, out_bound(ref, U * (p1.abs() + h1.abs())), f"bn_add_relu {rows}x{C}")
     # fmaf(c, sc, sh) + idt: k = 2
-    within(ops.bn_add_relu(cd, s3d, rows, C, idt=idd), torch.relu(p1 + h1 + i64), 2 * U * (p1.abs() + h1.abs() + i64.abs()),
+    ref = torch.relu(p1 + h1 + i64)
+    within(ops.bn_add_relu(cd, s3d, rows, C, idt=idd), ref, out_bound(ref, 2 * U * (p1.abs() + h1.abs() + i64.abs())),
            f"bn_add_relu + idt {rows}x{C}")
     # fmaf(c, sc, sh) + fmaf(idt, idsc, idsh): k = 2 along either branch (its fma, the sum)
-    within(ops.bn_add_relu(cd, s3d, rows, C, idt=idd, idsaved=sdd), torch.relu(p1 + h1 + p2 + h2),
-           2 * U * (p1.abs() + h1.abs() + p2.abs() + h2.abs()), f"bn_add_relu + idt + idsaved {rows}x{C}")
+    ref = torch.relu(p1 + h1 + p2 + h2)
+    within(ops.bn_add_relu(cd, s3d, rows, C, idt=idd, idsaved=sdd), ref,
+           out_bound(ref, 2 * U * (p1.abs() + h1.abs() + p2.abs() + h2.abs())), f"bn_add_relu + idt + idsaved {rows}x{C}")
     # bn_bwd_apply from hand-made coefficients: k0 * (dz - k1) - k2 * (c - mean): subtraction, product, final subtraction: k = 3
     dz = torch.randn(rows, C, generator=g)
     coef = torch.stack([s3[2], torch.randn(C, generator=g) * 0.1, torch.randn(C, generator=g) * 0.1])
@@ -419,23 +435,24 @@ def test_bottleneck_tail_and_bn_apply_past_the_grid_cap(dev, rows, C):
     _tail_case(ops, dev, rows, C, 810 + C)
 
 
-def _maxpool_case(ops, dev, N, H, W, C, seed, exact=True, loop_ref=True):
+def _maxpool_case(ops, dev, N, H, W, C, seed, exact=True, loop_ref=True, store=torch.float32):
+    """store: the storage of the pool's input c and of its output y (the arg-max bytes and the gradients do not depend on it)"""
     g = gen(seed)
     OH, OW = R.pool_out(H), R.pool_out(W)
     if exact:
         # sc in {0.5, 1, 2}, sh and c multiples of 1/16: sc * c + sh is exact in fp32, ties are true ties
         sc = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=g)]
         sh = torch.randint(-8, 9, (C,), generator=g).float() / 16
-        c = R.draw_grid(g, (N, H, W, C))
+        c = R.stored(R.draw_grid(g, (N, H, W, C)), store)        # (grid values are bf16 values: test_elem_edges_cpu.py)
     else:
         sc, sh = torch.randn(C, generator=g) * 0.5 + 1.0, torch.randn(C, generator=g) * 0.3
-        c = torch.randn(N, H, W, C, generator=g)
+        c = R.stored(torch.randn(N, H, W, C, generator=g), store)
     a = torch.relu(c.double() * sc.double() + sh.double())
     y_ref, am_ref = R.maxpool_ref(a)
     saved = saved_of(sc, sc, sc, sh, dev)
-    y, am = ops.maxpool_fwd(c.to(dev), saved, N, H, W, C)
+    y, am = ops.maxpool_fwd(c.to(store).to(dev), saved, N, H, W, C)
     what = f"maxpool {N}x{H}x{W}x{C} {'exact' if exact else 'random'}"
-    assert y.shape == (N, OH, OW, C)
+    assert y.shape == (N, OH, OW, C) and y.dtype == store
     if exact:
         assert torch.equal(y.double().cpu(), y_ref), what + ": y"
         assert torch.equal(am.cpu(), am_ref), what + ": arg-max is not the first maximum in row-major window order"
@@ -443,7 +460,11 @@ def _maxpool_case(ops, dev, N, H, W, C, seed, exact=True, loop_ref=True):
         # fmaxf(c * sc + sh, 0): a product and a sum, or one fused rounding: k = 2 over the window's largest |terms|; the maximum of
         # values each within e of the reference's is within e of the reference's maximum
         e = 2 * U * float(((c.double() * sc.double()).abs() + sh.double().abs()).max())
-        within(y, y_ref, e, what + ": y")
+        within(y, y_ref, e if store == torch.float32 else R.stored16_bound(y_ref, e), what + ": y")
+        if store == torch.bfloat16:
+            # the storage contract of test_bf16_gpu.py: the fp32 instantiation's y on the widened input, rounded once by torch
+            y32, am32 = ops.maxpool_fwd(c.to(dev), saved, N, H, W, C)
+            assert torch.equal(y, y32.bfloat16()) and torch.equal(am, am32), what + ": not the fp32 mode's result rounded once"
     dy = torch.randn(N, OH, OW, C, generator=g)
     # the gradient lands where the kernel's own arg-max says (checked above against the reference's where the data allow it)
     da_ref, ab = (R.maxpool_bwd_ref if loop_ref else R.maxpool_bwd_gather_ref)(dy, am.cpu(), H, W)
@@ -479,14 +500,14 @@ def test_gap_bwd_past_the_grid_cap(dev):
 POOL_SHAPES = [(1, 1, 1), (2, 1, 7), (2, 7, 1), (1, 2, 2), (3, 5, 8), (2, 9, 6)]
 
 
-def _pool_bn_bwd(ops, dev, c, sc, sh, am, dy, da, N, H, W, C, seed):
+def _pool_bn_bwd(ops, dev, c, sc, sh, am, dy, da, N, H, W, C, seed, store=torch.float32):
     """bn_bwd(pool=...): the pool's input gradient gathered inside the BatchNorm reduction -- dz bit-equal to maxpool_bwd followed
-    by the mask, sums inside the case A bound"""
+    by the mask, sums inside the case A bound.  store: the storage of c (given widened, as _maxpool_case returns it)"""
     g = gen(seed)
     rows = N * H * W
     mean, invstd = torch.randn(C, generator=g) * 0.3, torch.rand(C, generator=g) + 0.5
     saved = saved_of(mean, invstd, sc, sh, dev)
-    cd = c.to(dev)
+    cd = c.to(store).to(dev)
     dgm, dbt = torch.empty(C, device=dev), torch.empty(C, device=dev)
     ap = ops.bn_bwd(None, cd, saved, rows, C, rows, dgm, dbt, 2, fused=True, pool=(dy.to(dev), am, N, H, W))
     mask = ((c.double() * sc.double() + sh.double()) > 0).reshape(rows, C)
@@ -510,12 +531,11 @@ def test_maxpool_borders(dev, N, H, W, C):
             _pool_bn_bwd(ops, dev, c, sc, sh, am, dy, da, N, H, W, C, 950 + C)
 
 
-@pytest.mark.parametrize("C", [4, 64])
-def test_maxpool_ties(dev, C):
+def _maxpool_ties_case(ops, dev, C, store=torch.float32):
     """windows that are all zero after the ReLU, and windows with the same positive value at two or more positions (copied
     pre-activations, the same sc / sh in every channel): the first position in row-major window order is recorded, as
-    F.max_pool2d does (test_elem_edges_cpu.py holds the reference to that), and the gradient goes there alone"""
-    from oaprogressionmmf_amd import ops
+    F.max_pool2d does (test_elem_edges_cpu.py holds the reference to that), and the gradient goes there alone.
+    store: the storage of c and y (every value here is a bf16 value)"""
     N, H, W = 2, 9, 10
     g = gen(960)
     sc, sh = torch.full((C,), 0.5), torch.full((C,), 0.25)
@@ -523,11 +543,12 @@ def test_maxpool_ties(dev, C):
     c[0, :4] = -3.0                                  # relu(0.5 * -3 + 0.25) = 0: all-zero windows, arg-max = first valid position
     c[0, 5:8, 2:7] = c[0, 5:6, 2:3] .abs() + 1.0     # a 3 x 5 patch of one positive value: ties inside and across windows
     c[1, :, 1::2] = c[1, :, 0:-1:2]                  # every column equals its left neighbour
+    assert torch.equal(R.stored(c, store), c)
     a = torch.relu(c.double() * 0.5 + 0.25)
     y_ref, am_ref = R.maxpool_ref(a)
     assert int((y_ref == 0).sum()) > 0
-    y, am = ops.maxpool_fwd(c.to(dev), saved_of(sc, sc, sc, sh, dev), N, H, W, C)
-    assert torch.equal(y.double().cpu(), y_ref)
+    y, am = ops.maxpool_fwd(c.to(store).to(dev), saved_of(sc, sc, sc, sh, dev), N, H, W, C)
+    assert y.dtype == store and torch.equal(y.double().cpu(), y_ref)
     assert torch.equal(am.cpu(), am_ref), "a tie is not resolved to the first maximum in row-major window order"
     dy = torch.randn(N, R.pool_out(H), R.pool_out(W), C, generator=g)
     da_ref, ab = R.maxpool_bwd_ref(dy, am_ref, H, W)
@@ -536,7 +557,13 @@ def test_maxpool_ties(dev, C):
     a_leaf = a.clone().permute(0, 3, 1, 2).requires_grad_(True)
     F.max_pool2d(a_leaf, 3, 2, 1).backward(dy.double().permute(0, 3, 1, 2))
     within(da, a_leaf.grad.permute(0, 2, 3, 1), 3 * U * ab, "maxpool_bwd on ties vs float64 autograd")
-    _pool_bn_bwd(ops, dev, c, sc, sh, am, dy, da, N, H, W, C, 961)
+    _pool_bn_bwd(ops, dev, c, sc, sh, am, dy, da, N, H, W, C, 961, store=store)
+
+
+@pytest.mark.parametrize("C", [4, 64])
+def test_maxpool_ties(dev, C):
+    from oaprogressionmmf_amd import ops
+    _maxpool_ties_case(ops, dev, C)
 
 
 @pytest.mark.parametrize("W", [1, 5, 7, 15, 16, 17])
