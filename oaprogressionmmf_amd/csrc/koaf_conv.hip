@@ -1,6 +1,7 @@
 // koaf_conv.hip -- dense and grouped convolution entry points built on koaf_gemm: the operand descriptors of the forward pass, the
 // data gradients and the weight gradients (split-K plan: wgrad_plan), plus the grouped-conv weight expansion.
 #include "koaf_common.h"
+#include "koaf_conv_units.h"
 
 namespace {
 
@@ -116,47 +117,7 @@ __global__ void __launch_bounds__(256) gconv_compress_kernel(const float* __rest
 // ================================================================================================
 // dense convolution
 // ================================================================================================
-// koaf_fwd_s2.hip: the stride-2 forward convolutions (1x1 / pad 0, 3x3 / pad 1) over the fp32 tensors on 256-row tiles, bit-identical to
-// koaf_gemm_kernel on the same descriptor
-int koaf_fwd_s2(const KoafGemm& g, void* stream);
-// does koaf_fwd_s2 take the forward convolution described by g?  The fp16 scheme with the F plane image, fp32 tensors at pixel stride Cin,
-// no plane-image input, tail or emission, whole k-tiles inside a tap (Cin % 32 == 0), whole column tiles (Cout % 128 == 0), whole 256-row
-// tiles (M % 256 == 0: a ragged last tile stays with the generic kernel, and so do the 128-row tiles its small calls are tested on),
-// 16-B aligned pointers, a source pixel index that fits 31 bits and, behind a prologue, no more channels than the kernel's coefficient
-// table holds (1024).  One k-tile is the shortest K the pipeline is written for.
-static inline bool fwd_s2_ok(const KoafGemm& g, int KH, int KW, int stride, int pad, bool x_planes, bool tail, bool emit) {
-    const KoafOperand& A = g.A;
-    if (stride != 2 || KH != KW || !((KH == 1 && pad == 0) || (KH == 3 && pad == 1))) return false;
-    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || g.act16 != 0 || x_planes || tail || emit) return false;
-    if (A.kind != 0 || A.gather != 1 || A.amax || (A.C % 32) != 0 || A.CS != A.C || (g.N % 128) != 0 || (g.M % 256) != 0 || g.K < 32) return false;
-    if (A.tf != 0 && (A.tf != 1 || A.C > 1024 || !aligned16(A.sc) || !aligned16(A.sh))) return false;
-    if (!aligned16(A.ptr) || !aligned16(g.B.planes) || !aligned16(g.C)) return false;
-    return (int64_t)(g.M / (A.PH * A.PW)) * A.H * A.W < (1ll << 31);
-}
-
-// koaf_fwd1.hip: the dense 1x1 / stride-1 forward convolutions over the fp32 tensors on 256-row tiles, bit-identical to koaf_gemm_kernel on
-// the same descriptor; koaf_fwd1_form: the form a (Cin, Cout) ships in (0 one tile per block, 1 the persistent walk), -1 for none
-int koaf_fwd1(const KoafGemm& g, int form, void* stream);
-int koaf_fwd1_form(int K, int N);
-bool koaf_stream_on();      // koaf_gemm.hip: koaf_set_stream's switch
-// the form in which koaf_fwd1 takes the forward convolution described by g, -1 if it does not.  A pointwise call of the fp16 scheme with
-// the F plane image, fp32 tensors at pixel stride Cin, no plane-image input, tail or emission, whole k-tiles and at least two of them
-// (Cin % 32 == 0, K >= 64), whole column tiles (Cout % 128 == 0), 16-B aligned pointers, behind a prologue no more channels than the
-// coefficient table holds (1024), the streamed kernels switched on (koaf_set_stream(0) keeps these calls on the block-wide loader) --
-// and whole 256-row tiles, at least one per CU (M % 256 == 0, M >= 65536): below that a 256-row tiling cannot fill the chip, and the
-// small calls the tests pin to koaf_gemm/stream from their launch records stay there.  Among these, the (Cin, Cout) of koaf_fwd1_form's
-// table: the production shapes that passed the per-call rule.
-static inline int fwd1_ok(const KoafGemm& g, int KH, int KW, int stride, int pad, bool x_planes, bool tail, bool emit) {
-    const KoafOperand& A = g.A;
-    if (!is_pointwise(KH, KW, stride, pad) || !koaf_stream_on()) return -1;
-    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || g.act16 != 0 || x_planes || tail || emit) return -1;
-    if (A.kind != 0 || A.gather != 0 || A.amax || A.ld != g.K || (g.K % 32) != 0 || g.K < 64 || (g.N % 128) != 0) return -1;
-    if ((g.M % 256) != 0 || g.M < 65536) return -1;
-    if (A.tf != 0 && (A.tf != 1 || g.K > 1024 || !aligned16(A.sc) || !aligned16(A.sh))) return -1;
-    if (!aligned16(A.ptr) || !aligned16(g.B.planes) || !aligned16(g.C)) return -1;
-    return koaf_fwd1_form(g.K, g.N);
-}
-
+// (the 256-row units and their dispatch rules: koaf_conv_units.h; each rule is written next to its kernel)
 extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t N, int32_t H, int32_t W, int32_t Cin,
                                int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* in_sc,
                                const float* in_sh, float* stats, int32_t* stats_rows, const float* stats_shift,
@@ -199,13 +160,10 @@ extern "C" int koaf_conv2d_fwd(const float* x, const float* w, float* y, int32_t
         KOAF_REQUIRE(emit->planes && emit->sc && emit->sh && (Cout % 8) == 0, "koaf_conv2d_fwd: emit needs planes / sc / sh and Cout %% 8 == 0");
         g.out_planes = emit->planes; g.out_sc = emit->sc; g.out_sh = emit->sh; g.out_ps = M * Cout;
     }
-    if (fwd_s2_ok(g, KH, KW, stride, pad, x_planes != nullptr, tail != nullptr, emit != nullptr)) {
+    const bool s2 = koaf_fwd_s2_ok(g);
+    if (s2 || koaf_fwd1_ok(g) >= 0) {
         if (stats_rows) *stats_rows = g.M / 128;        // two partial rows per 256-row tile: the rows of a 128-row tiling
-        return koaf_fwd_s2(g, stream);
-    }
-    if (const int form = fwd1_ok(g, KH, KW, stride, pad, x_planes != nullptr, tail != nullptr, emit != nullptr); form >= 0) {
-        if (stats_rows) *stats_rows = g.M / 128;
-        return koaf_fwd1(g, form, stream);
+        return s2 ? koaf_fwd_s2(g, stream) : koaf_fwd1(g, stream);
     }
     if (stats_rows) *stats_rows = koaf_gemm_part_rows(&g);
     return koaf_gemm(&g, stream);
@@ -240,30 +198,6 @@ extern "C" int32_t koaf_conv2d_dgrad_bnb_rows(int32_t N, int32_t H, int32_t W, i
         return (int32_t)r;
     }
     return (int32_t)cdiv64((int64_t)N * H * W, 64);
-}
-
-// koaf_dgrad_s2.hip: one parity class of a stride-2 data gradient (3x3 / pad 1 over dy's plane images; class (0, 0) of a 1x1 / pad 0
-// shortcut over the fp32 tensors, with the zeros of the three classes without a tap) on 256-row tiles, bit-identical to koaf_gemm_kernel
-// on the same class descriptors
-int koaf_dgrad_s2(const KoafGemm& g, void* stream);
-// does koaf_dgrad_s2 take the class described by g (and with it the whole call: the rule reads nothing that differs between the classes
-// that have a tap)?  The fp16 scheme with the D plane image on fp32 tensors, no residual, no fused reduction or mode 2 with one
-// BatchNorm; 3x3 / pad 1 from dy's plane images (reduction optional), 1x1 / pad 0 from the fp32 dy (tf 0 | 2) without a reduction; whole
-// k-tiles inside a tap (Cout % 32 == 0), whole column tiles (Cin % 128 == 0); an even image whose classes are whole 256-row tiles (a ragged
-// tile or an odd image stays with the generic kernel, and so do the 128-row tiles its small calls are tested on); 16-B aligned pointers.
-// (Pixel indices fit 31 bits: koaf_conv2d_dgrad_bnb requires N H W < 2^31.)
-static inline bool dgrad_s2_ok(const KoafGemm& g, int KH, int KW, int pad, int H, int W, const KoafBnb* bnb, bool dy_planes) {
-    const KoafOperand& A = g.A;
-    const bool f11 = KH == 1 && KW == 1 && pad == 0, f33 = KH == 3 && KW == 3 && pad == 1;
-    if (!(f11 || f33) || (H & 1) || (W & 1) || (g.M % 256) != 0 || g.K < 32) return false;
-    if (g.fmt != 1 || g.B.kind != 2 || !g.B.planes || !g.B.amax || !A.amax || g.act16 != 0 || g.residual) return false;
-    if ((A.C % 32) != 0 || (g.N % 128) != 0 || !aligned16(g.C) || !aligned16(g.B.planes)) return false;
-    if (bnb && (bnb->mode != 2 || bnb->c2 || !aligned16(bnb->c) || !aligned16(bnb->sc) || !aligned16(bnb->sh) || !aligned16(bnb->mean) ||
-                !aligned16(bnb->invstd) || !aligned16(g.bnb_part)))
-        return false;
-    if (f33) return dy_planes && A.kind == 2 && aligned16(A.planes) && aligned16(A.zeros) && !(A.plane_stride & 7);
-    if (dy_planes || bnb || A.kind != 0 || !aligned16(A.ptr)) return false;
-    return A.tf == 0 || (A.tf == 2 && aligned16(A.ptr2) && aligned16(A.sc) && aligned16(A.sh) && aligned16(A.sc2));
 }
 
 extern "C" int koaf_conv2d_dgrad_bnb(const float* dy, const float* w, float* dx, int32_t N, int32_t H, int32_t W,
@@ -329,9 +263,9 @@ extern "C" int koaf_conv2d_dgrad_bnb(const float* dy, const float* w, float* dx,
                 g.cmap = 1; g.cm_PH = Hc; g.cm_PW = Wc; g.cm_H = H; g.cm_W = W; g.cm_py = py; g.cm_px = px;
                 g.act16 = act16 ? 2 : 0;
                 if (bnb) set_bnb(&g, bnb, part + (int64_t)rows_done * nsum * Cin);
-                if (dgrad_s2_ok(g, KH, KW, pad, H, W, bnb, dy_planes != nullptr)) {
+                if (koaf_dgrad_s2_ok(g, KH, KW)) {
                     if (bnb) rows_done += g.M / 128;        // two partial rows per 256-row tile: the rows of a 128-row tiling
-                    int rc = koaf_dgrad_s2(g, stream);
+                    int rc = koaf_dgrad_s2(g, KH, KW, stream);
                     if (rc != KOAF_OK) return rc;
                     all_done = KH == 1;
                     continue;
@@ -389,42 +323,8 @@ extern "C" int koaf_conv2d_dgrad(const float* dy, const float* w, float* dx, int
                                  nullptr, wimg, dy_amax, dy_apply, dy_planes, act16, stream);
 }
 
-// koaf_wgrad3.hip: 3x3 / stride 1 / pad 1 over plane images, both tensors walked once in padded raster order
-bool koaf_wgrad3_ring_ok(int N, int H, int W, int Cin, int Cout);
-int64_t koaf_wgrad3_ring_ws(int N, int H, int W, int Cin, int Cout);
-int koaf_wgrad3_ring(const uint16_t* dy_planes, const uint16_t* x_planes, float* dw, float* slabs, const float* dy_amax,
-                     float x_scale, int N, int H, int W, int Cin, int Cout, void* stream);
 static inline bool wgrad3_ring_shape(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     return KH == 3 && KW == 3 && stride == 1 && pad == 1 && koaf_wgrad3_ring_ok(N, H, W, Cin, Cout);
-}
-
-// koaf_wgrad1.hip: 1x1 / stride 1, and stride 2 (1x1 / pad 0, 3x3 / pad 1), over the fp32 tensors on 256-wide tiles, same split-K plan and slabs
-int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream);
-// the tile on which koaf_wgrad1 takes the weight gradient described by g under plan p (bm = 0: the generic kernel keeps it): the fp16
-// scheme on fp32 tensors, channel counts in whole tiles of 128 with at least one side 256 wide, and k-ranges of at least WGRAD1_MIN_KCHUNK
-// pixels -- shorter launches stay with the generic kernel's more and smaller blocks.  B is dense (1x1 / stride 1) or the stride-2 gather
-// of a 1x1 / pad 0 or 3x3 / pad 1 filter whose Cin is a whole number of column tiles (a block then works on one filter tap); layer2's
-// 3x3 / stride 2 at 128 -> 128 (N = 1152: no whole number of 256-wide tiles beside M = 128) and every other gather stay on koaf_gemm
-constexpr int WGRAD1_MIN_KCHUNK = 1024;
-static inline WgradPlan wgrad1_tile(const KoafGemm& g, const WgradPlan& p) {
-    WgradPlan t = {0, 0, p.splitk};
-    const KoafOperand& B = g.B;
-    if (g.fmt != 1 || g.act16 != 0 || g.A.kind != 1 || B.kind != 1 || g.A.gather || (B.gather != 0 && B.gather != 1)) return t;
-    if (g.M % 128 || g.N % 128 || (g.M < 256 && g.N < 256)) return t;
-    const int bm = g.M >= 256 ? 256 : 128, bn = g.N >= 256 ? 256 : 128;
-    if (g.M % bm || g.N % bn) return t;
-    if (B.gather == 1) {
-        const bool f11 = B.KH == 1 && B.KW == 1 && B.pad == 0 && B.pad_w == 0, f33 = B.KH == 3 && B.KW == 3 && B.pad == 1 && B.pad_w == 1;
-        if (B.stride != 2 || !(f11 || f33) || B.CS != B.C || B.C % bn || B.PH <= 0 || B.PW <= 0) return t;
-        if ((int64_t)(g.K / (B.PH * B.PW)) * B.H * B.W >= (1ll << 31)) return t;      // (the kernel's table holds 31-bit pixel indices)
-    }
-    if (rup32(cdiv64(g.K, p.splitk)) < WGRAD1_MIN_KCHUNK) return t;
-    // (what koaf_gemm's vector path asks of the pointers; an unaligned call takes the generic kernel's scalar path)
-    if (!aligned16(g.A.ptr) || !aligned16(g.B.ptr) || !aligned16(g.C)) return t;
-    if (g.A.tf && (!aligned16(g.A.ptr2) || !aligned16(g.A.sc) || !aligned16(g.A.sh) || !aligned16(g.A.sc2))) return t;
-    if (g.B.tf && (!aligned16(g.B.sc) || !aligned16(g.B.sh))) return t;
-    t.bm = bm; t.bn = bn;
-    return t;
 }
 
 extern "C" int64_t koaf_conv2d_wgrad_ws(int32_t N, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t KH,
@@ -484,8 +384,7 @@ extern "C" int koaf_conv2d_wgrad(const float* dy, const float* x, float* dw, int
     g.C = p.splitk > 1 ? slabs : dw;
     g.ldc = Ntot;
     g.act16 = (act16 && !dy_planes) ? 3 : 0;      // (x and dy_apply->c are bf16 activations; plane images carry no storage type)
-    const WgradPlan t1 = wgrad1_tile(g, p);
-    int rc = t1.bm ? koaf_wgrad1(g, t1.bm, t1.bn, stream) : koaf_gemm(&g, stream);
+    int rc = koaf_wgrad1_ok(g) ? koaf_wgrad1(g, stream) : koaf_gemm(&g, stream);
     if (rc != KOAF_OK || p.splitk == 1) return rc;
     return koaf_slab_reduce(slabs, p.splitk, (int64_t)Cout * Ntot, dw, stream);
 }

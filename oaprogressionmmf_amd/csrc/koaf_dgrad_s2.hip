@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include "koaf.h"
 #include "koaf_tile256.h"
+#include "koaf_conv_units.h"
 
 namespace {
 struct Ds2Params {
@@ -322,30 +323,49 @@ int ds2_launch(const Ds2Params& p, int am, dim3 grid, hipStream_t s) {
 }
 }  // namespace
 
+// does koaf_dgrad_s2 take the class described by g of a KH x KW filter (and with it the whole call: the rule reads nothing that differs
+// between the classes that have a tap)?  The fp16 scheme with the D plane image on fp32 tensors, no residual, no fused reduction or mode 2
+// with one BatchNorm; 3x3 / pad 1 from dy's plane images (reduction optional), 1x1 / pad 0 from the fp32 dy (tf 0 | 2) without a reduction;
+// whole k-tiles inside a tap (Cout % BK == 0), whole column tiles (Cin % 128 == 0); an even image whose classes are whole 256-row tiles (a
+// ragged tile or an odd image stays with the generic kernel, and so do the 128-row tiles its small calls are tested on); 16-B aligned
+// pointers; pixel indices that fit 31 bits.  The descriptor carries the class, not the call: pad 1 of a 3x3 is read from the class's taps
+// and offsets (class (py, px) has 1 + py by 1 + px taps at offsets py, px); the filter size is given, since class (0, 0) of a 3x3 and of a
+// 1x1 both have one tap.  A class without a tap (K = 0) is refused: the 1x1 call's class (0, 0) writes its zeros.
+bool koaf_dgrad_s2_ok(const KoafGemm& g, int KH, int KW) {
+    const KoafOperand& A = g.A;
+    const KoafOperand& B = g.B;
+    const bool f11 = KH == 1 && KW == 1, f33 = KH == 3 && KW == 3;
+    if (!(f11 || f33) || g.fmt != 1 || g.act16 != 0 || A.gather != 2 || !A.amax || A.stride != 1) return false;
+    if (B.kind != 2 || B.gather != 0 || !B.planes || !B.amax || B.tf || !g.C || g.ldc != g.N || g.splitk > 1 || g.nb0 * g.nb1 > 1) return false;
+    if (g.bias || g.residual || !g.cmap || g.stats || g.out_planes || g.m_base != 0 || !aligned16(g.C) || !aligned16(B.planes)) return false;
+    if (g.M % T256_BM != 0 || g.N % 128 != 0 || g.K < BK || A.C % BK != 0 || A.KH <= 0 || A.KW <= 0 || g.K != A.KH * A.KW * A.C || A.CS != A.C) return false;
+    // the row map: an even image (cm_H = 2 PH), whole images per class
+    if (A.PH <= 0 || A.PW <= 0 || g.cm_PH != A.PH || g.cm_PW != A.PW || g.cm_H != 2 * A.PH || g.cm_W != 2 * A.PW || g.M % (A.PH * A.PW) != 0 ||
+        (int64_t)(g.M / (A.PH * A.PW)) * g.cm_H * g.cm_W >= (1ll << 31) || (unsigned)g.cm_py >= 2u || (unsigned)g.cm_px >= 2u)
+        return false;
+    if (g.bnb_mode && (g.bnb_mode != 2 || g.bnb2_c || !g.bnb_c || !g.bnb_sc || !g.bnb_sh || !g.bnb_mean || !g.bnb_invstd || !g.bnb_part ||
+                       !aligned16(g.bnb_c) || !aligned16(g.bnb_sc) || !aligned16(g.bnb_sh) || !aligned16(g.bnb_mean) || !aligned16(g.bnb_invstd) ||
+                       !aligned16(g.bnb_part)))
+        return false;
+    if (f33)      // pad 1, from dy's plane images
+        return A.kind == 2 && A.planes && A.zeros && !A.tf && aligned16(A.planes) && aligned16(A.zeros) && !(A.plane_stride & 7) &&
+               A.KH == 1 + g.cm_py && A.KW == 1 + g.cm_px && A.pad == g.cm_py && A.pad_w == g.cm_px;
+    // fp32 A: the identity walk of class (0, 0) of a 1x1 / pad 0 filter, without a fused reduction
+    if (A.kind != 0 || !A.ptr || !aligned16(A.ptr) || A.KH != 1 || A.KW != 1 || A.pad != 0 || A.pad_w != 0 || A.H != A.PH || A.W != A.PW ||
+        g.cm_py != 0 || g.cm_px != 0 || g.bnb_mode)
+        return false;
+    return A.tf == 0 || (A.tf == 2 && A.ptr2 && A.sc && A.sh && A.sc2 && aligned16(A.ptr2) && aligned16(A.sc) && aligned16(A.sh) && aligned16(A.sc2));
+}
+
 // One parity class of a stride-2 data gradient, described by g as koaf_conv2d_dgrad_bnb builds it (A = dy with gather 2 at stride 1, from
 // plane images or fp32 with tf 0 | 2; B = the class's taps of the D plane image; the row map; BatchNorm-backward mode 2 optional), on
-// 256-row tiles; the caller has checked the dispatch rule (koaf_conv.hip dgrad_s2_ok).  A call whose A is fp32 is class (0, 0) of a 1x1
-// shortcut: it also writes the zeros of the three classes without a tap and leaves their launch records (K = 0) behind its own.
-int koaf_dgrad_s2(const KoafGemm& g, void* stream) {
+// 256-row tiles.  A call whose A is fp32 is class (0, 0) of a 1x1 shortcut: it also writes the zeros of the three classes without a tap
+// and leaves their launch records (K = 0) behind its own.
+int koaf_dgrad_s2(const KoafGemm& g, int KH, int KW, void* stream) {
     const KoafOperand& A = g.A;
     const KoafOperand& B = g.B;
     const bool pl = A.kind == 2;
-    KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && A.gather == 2 && A.amax && A.stride == 1 && B.kind == 2 && B.gather == 0 && B.planes && B.amax &&
-                 !B.tf && g.C && g.ldc == g.N && g.splitk <= 1 && g.nb0 * g.nb1 <= 1 && !g.bias && !g.residual && g.cmap && !g.stats &&
-                 !g.out_planes && g.m_base == 0 && g.M % T256_BM == 0 && g.N % 128 == 0 && A.C % BK == 0 && A.KH > 0 && A.KW > 0 &&
-                 g.K == A.KH * A.KW * A.C && (A.CS == 0 || A.CS == A.C),
-                 "koaf_dgrad_s2: bad args");
-    KOAF_REQUIRE(pl ? (A.planes && A.zeros && !A.tf) : (A.kind == 0 && A.ptr && (A.tf == 0 || (A.tf == 2 && A.ptr2 && A.sc && A.sh && A.sc2))),
-                 "koaf_dgrad_s2: bad A operand");
-    KOAF_REQUIRE(g.cm_PH == A.PH && g.cm_PW == A.PW && g.cm_H == 2 * A.PH && g.cm_W == 2 * A.PW && g.M % (A.PH * A.PW) == 0 &&
-                 (int64_t)(g.M / (A.PH * A.PW)) * g.cm_H * g.cm_W < (1ll << 31) && (unsigned)g.cm_py < 2u && (unsigned)g.cm_px < 2u,
-                 "koaf_dgrad_s2: bad row map");
-    // fp32 A: the identity walk of class (0, 0) of a 1x1 / pad 0 filter
-    KOAF_REQUIRE(pl || (A.KH == 1 && A.KW == 1 && A.pad == 0 && A.pad_w == 0 && A.H == A.PH && A.W == A.PW && g.cm_py == 0 && g.cm_px == 0 &&
-                        !g.bnb_mode),
-                 "koaf_dgrad_s2: fp32 A is the 1x1 shortcut's class (0, 0), without a fused reduction");
-    KOAF_REQUIRE(!g.bnb_mode || (g.bnb_mode == 2 && !g.bnb2_c && g.bnb_c && g.bnb_sc && g.bnb_sh && g.bnb_mean && g.bnb_invstd && g.bnb_part),
-                 "koaf_dgrad_s2: the fused reduction is mode 2 with one BatchNorm");
+    KOAF_REQUIRE(koaf_dgrad_s2_ok(g, KH, KW), "koaf_dgrad_s2: bad args");
     Ds2Params p;
     p.dz = A.ptr; p.c = A.ptr2; p.sc = A.sc; p.sc2 = A.sc2; p.sh = A.sh; p.a_amax = A.amax;
     p.apl = A.planes; p.a_ps = A.plane_stride; p.azero = A.zeros;

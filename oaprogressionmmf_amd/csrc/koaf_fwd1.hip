@@ -21,6 +21,7 @@
 #include <type_traits>
 #include "koaf.h"
 #include "koaf_tile256.h"
+#include "koaf_conv_units.h"
 
 namespace {
 struct F1Params : T256FwdParams {       // x is [M][K]
@@ -30,6 +31,7 @@ struct F1Params : T256FwdParams {       // x is [M][K]
 };
 
 constexpr int F1_CUS = 256;              // WALK 1: one block per CU
+constexpr int F1_MAX_K = 8192;           // the rule's cap on Cin: longer rows were never admitted, timed or tested
 
 template <int BN, int TF, int WALK>
 __global__ void __launch_bounds__(T256_NT) fwd1_kernel(const F1Params p) {
@@ -235,13 +237,27 @@ int koaf_fwd1_form(int K, int N) {
 #endif
 }
 
-// the 1x1 / stride-1 forward convolution described by g (koaf_conv2d_fwd's descriptor: A = x dense with tf 0 | 1, B = the F plane image,
-// fmt 1, act16 0, statistics optional) on 256-row tiles in the given form; the caller has checked the dispatch rule (koaf_conv.hip fwd1_ok)
-int koaf_fwd1(const KoafGemm& g, int form, void* stream) {
+// the form in which koaf_fwd1 takes the forward convolution described by g, -1 if it does not.  A pointwise call of the fp16 scheme with
+// the F plane image, fp32 tensors at pixel stride Cin, no plane-image input, tail or emission, whole k-tiles and at least two of them
+// (Cin % BK == 0, K >= 2 BK: the walk's last-but-one k-step exists), whole column tiles (Cout % 128 == 0), 16-B aligned pointers
+// (t256_fwd_args_ok), no more than F1_MAX_K channels and, behind a prologue, no more than the coefficient table holds (T256_TAB_C), the
+// streamed kernels switched on (koaf_set_stream(0) keeps these calls on the block-wide loader) -- and whole 256-row tiles, at least one
+// per CU (M % T256_BM == 0, M >= F1_CUS T256_BM = 65536): below that a 256-row tiling cannot fill the chip, and the small calls the
+// tests pin to koaf_gemm/stream from their launch records stay there.  Among these, the (Cin, Cout) of koaf_fwd1_form's table: the
+// production shapes that passed the per-call rule.
+int koaf_fwd1_ok(const KoafGemm& g) {
     const KoafOperand& A = g.A;
-    KOAF_REQUIRE(t256_fwd_args_ok(g) && A.gather == 0 && !A.ptr2 && (A.tf == 0 || g.K <= T256_TAB_C) && A.ld == g.K && g.K >= 2 * BK && g.K <= 8192 &&
-                 (form == 0 || form == 1),
-                 "koaf_fwd1: bad args");
+    if (!t256_fwd_args_ok(g) || A.gather != 0 || A.ld != g.K || !koaf_stream_on()) return -1;
+    if (g.K < 2 * BK || g.K > F1_MAX_K || (A.tf != 0 && g.K > T256_TAB_C) || g.M < F1_CUS * T256_BM) return -1;
+    return koaf_fwd1_form(g.K, g.N);
+}
+
+// the 1x1 / stride-1 forward convolution described by g (koaf_conv2d_fwd's descriptor: A = x dense with tf 0 | 1, B = the F plane image,
+// fmt 1, act16 0, statistics optional) on 256-row tiles, in the form the rule names
+int koaf_fwd1(const KoafGemm& g, void* stream) {
+    const KoafOperand& A = g.A;
+    const int form = koaf_fwd1_ok(g);
+    KOAF_REQUIRE(form == 0 || form == 1, "koaf_fwd1: bad args");
     F1Params p;
     t256_fwd_params(g, p);
     p.M = g.M; p.N = g.N; p.K = g.K;

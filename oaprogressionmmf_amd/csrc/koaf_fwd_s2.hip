@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include "koaf.h"
 #include "koaf_tile256.h"
+#include "koaf_conv_units.h"
 
 namespace {
 struct Fs2Params : T256FwdParams {      // x is [n][H][W][C]
@@ -164,16 +165,26 @@ int fs2_launch(const Fs2Params& p, int tf, dim3 grid, hipStream_t s) {
 }
 }  // namespace
 
+// does koaf_fwd_s2 take the forward convolution described by g?  A stride-2 call, 1x1 / pad 0 or 3x3 / pad 1, of the fp16 scheme with the
+// F plane image, fp32 tensors at pixel stride Cin, no plane-image input, tail or emission, whole k-tiles inside a tap (Cin % BK == 0),
+// whole column tiles (Cout % 128 == 0), whole 256-row tiles (M % T256_BM == 0: a ragged last tile stays with the generic kernel, and so
+// do the 128-row tiles its small calls are tested on), 16-B aligned pointers (t256_fwd_args_ok), a source pixel index that fits 31 bits
+// and, behind a prologue, no more channels than the kernel's coefficient table holds (T256_TAB_C).  One k-tile is the shortest K the
+// pipeline is written for.
+bool koaf_fwd_s2_ok(const KoafGemm& g) {
+    const KoafOperand& A = g.A;
+    if (!t256_fwd_args_ok(g) || A.gather != 1 || g.K < BK) return false;
+    if (A.stride != 2 || A.KH != A.KW || A.pad != A.pad_w || !((A.KH == 1 && A.pad == 0) || (A.KH == 3 && A.pad == 1))) return false;
+    if (A.C % BK != 0 || A.CS != A.C || g.K != A.KH * A.KW * A.C || (A.tf != 0 && A.C > T256_TAB_C)) return false;
+    if (A.PH <= 0 || A.PW <= 0 || A.PH != (A.H + 2 * A.pad - A.KH) / 2 + 1 || A.PW != (A.W + 2 * A.pad_w - A.KW) / 2 + 1) return false;
+    return g.M % (A.PH * A.PW) == 0 && (int64_t)(g.M / (A.PH * A.PW)) * A.H * A.W < (1ll << 31);
+}
+
 // the stride-2 forward convolution described by g (koaf_conv2d_fwd's descriptor: A = x with gather 1 and tf 0 | 1, B = the F plane image,
-// fmt 1, act16 0, statistics optional) on 256-row tiles; the caller has checked the dispatch rule (koaf_conv.hip fwd_s2_ok)
+// fmt 1, act16 0, statistics optional) on 256-row tiles
 int koaf_fwd_s2(const KoafGemm& g, void* stream) {
     const KoafOperand& A = g.A;
-    KOAF_REQUIRE(t256_fwd_args_ok(g) && A.gather == 1 && g.K >= BK, "koaf_fwd_s2: bad args");
-    KOAF_REQUIRE(A.stride == 2 && A.KH == A.KW && A.pad == A.pad_w && ((A.KH == 1 && A.pad == 0) || (A.KH == 3 && A.pad == 1)) && A.C % BK == 0 &&
-                 (A.CS == 0 || A.CS == A.C) && g.K == A.KH * A.KW * A.C && A.PH > 0 && A.PW > 0 && A.PH == (A.H + 2 * A.pad - A.KH) / 2 + 1 &&
-                 A.PW == (A.W + 2 * A.pad_w - A.KW) / 2 + 1 && g.M % (A.PH * A.PW) == 0 &&
-                 (int64_t)(g.M / (A.PH * A.PW)) * A.H * A.W < (1ll << 31) && (A.tf == 0 || A.C <= T256_TAB_C),
-                 "koaf_fwd_s2: bad gather");
+    KOAF_REQUIRE(koaf_fwd_s2_ok(g), "koaf_fwd_s2: bad args");
     Fs2Params p;
     t256_fwd_params(g, p);
     p.M = g.M; p.N = g.N; p.K = g.K;

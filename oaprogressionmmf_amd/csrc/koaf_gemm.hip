@@ -123,7 +123,7 @@ bool stream_ok(const KoafGemm& g) {
 }
 }  // namespace
 
-// koaf_set_stream's switch for the dispatch rules outside this file (koaf_conv.hip fwd1_ok)
+// koaf_set_stream's switch for the dispatch rules outside this file (koaf_fwd1.hip koaf_fwd1_ok)
 bool koaf_stream_on() { return g_stream_mode == 1; }
 
 extern "C" int koaf_gemm_pick_tile(const KoafGemm* g, int32_t* bm, int32_t* bn) {

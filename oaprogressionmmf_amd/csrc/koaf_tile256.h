@@ -254,15 +254,18 @@ struct T256FwdParams {
 
 // ---- host side ----
 
-// what koaf_fwd1 and koaf_fwd_s2 both require of a descriptor: A fp32 with tf 0 | 1 at a fixed scale, B the F plane image, a plain
-// output with optional statistics, whole tiles and k-tiles
+// what koaf_fwd1 and koaf_fwd_s2 both require of a descriptor: the fp16 scheme on fp32 tensors, A fp32 with tf 0 | 1 at a fixed scale (no
+// plane-image input, no tail), B the F plane image, a plain output with optional statistics (no emission), whole tiles and k-tiles,
+// 16-B aligned pointers
 inline bool t256_fwd_args_ok(const KoafGemm& g) {
     const KoafOperand& A = g.A;
     const KoafOperand& B = g.B;
-    return g.fmt == 1 && g.act16 == 0 && A.kind == 0 && A.ptr && !A.amax && (A.tf == 0 || (A.tf == 1 && A.sc && A.sh)) &&
+    return g.fmt == 1 && g.act16 == 0 && A.kind == 0 && A.ptr && !A.ptr2 && !A.amax &&
+           (A.tf == 0 || (A.tf == 1 && A.sc && A.sh && aligned16(A.sc) && aligned16(A.sh))) &&
            B.kind == 2 && B.gather == 0 && B.planes && B.amax && !B.tf && g.C && g.ldc == g.N && g.splitk <= 1 && g.nb0 * g.nb1 <= 1 &&
            !g.bias && !g.residual && !g.cmap && !g.bnb_mode && !g.out_planes && g.m_base == 0 && g.stats_bs == 0 &&
-           g.M % T256_BM == 0 && g.N % 128 == 0 && g.K % BK == 0 && B.ld == g.K;
+           g.M % T256_BM == 0 && g.N % 128 == 0 && g.K % BK == 0 && B.ld == g.K &&
+           aligned16(A.ptr) && aligned16(B.planes) && aligned16(g.C);
 }
 inline void t256_fwd_params(const KoafGemm& g, T256FwdParams& p) {
     const KoafOperand& A = g.A;

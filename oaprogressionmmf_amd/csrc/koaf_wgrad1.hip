@@ -21,6 +21,7 @@
 #include <type_traits>
 #include "koaf.h"
 #include "koaf_tile256.h"
+#include "koaf_conv_units.h"
 
 namespace {
 struct Wg1Params {
@@ -279,24 +280,44 @@ int wg1_tile(const Wg1Params& p, int bm, int bn, int tfa, int tfb, dim3 grid, hi
 }
 }  // namespace
 
+// does koaf_wgrad1 take the weight gradient described by g, split g.splitk ways, and on which tile (bm_ / bn_, optional)?  The
+// fp16 scheme on fp32 tensors, channel counts in whole tiles of 128 with at least one side 256 wide, and k-ranges of at least
+// WGRAD1_MIN_KCHUNK pixels -- shorter launches stay with the generic kernel's more and smaller blocks.  B is dense (1x1 / stride 1) or the
+// stride-2 gather of a 1x1 / pad 0 or 3x3 / pad 1 filter over whole pixels whose Cin is a whole number of column tiles (a block then works
+// on one filter tap), k = whole images of the output grid and a source pixel index that fits the table's 31 bits; layer2's 3x3 / stride 2
+// at 128 -> 128 (N = 1152: no whole number of 256-wide tiles beside M = 128) and every other gather stay on koaf_gemm
+constexpr int WGRAD1_MIN_KCHUNK = 1024;
+bool koaf_wgrad1_ok(const KoafGemm& g, int* bm_, int* bn_) {
+    const KoafOperand& A = g.A;
+    const KoafOperand& B = g.B;
+    if (g.fmt != 1 || g.act16 != 0 || A.kind != 1 || B.kind != 1 || A.gather || (B.gather != 0 && B.gather != 1)) return false;
+    if (!A.amax || !A.ptr || !B.ptr || !g.C || g.K < BK || g.K >= (1 << 30) || g.splitk < 1 || g.splitk > 65535) return false;
+    if (g.M % 128 || g.N % 128 || (g.M < 256 && g.N < 256)) return false;
+    const int bm = g.M >= 256 ? 256 : 128, bn = g.N >= 256 ? 256 : 128;
+    if (g.M % bm || g.N % bn || A.ld != g.M || g.ldc != g.N || (B.gather == 0 && B.ld != g.N)) return false;
+    if (B.gather == 1) {
+        const bool f11 = B.KH == 1 && B.KW == 1 && B.pad == 0 && B.pad_w == 0, f33 = B.KH == 3 && B.KW == 3 && B.pad == 1 && B.pad_w == 1;
+        if (B.stride != 2 || !(f11 || f33) || B.CS != B.C || B.C % bn || g.N != B.KH * B.KW * B.C || B.PH <= 0 || B.PW <= 0) return false;
+        if (B.PH != (B.H + 2 * B.pad - B.KH) / 2 + 1 || B.PW != (B.W + 2 * B.pad_w - B.KW) / 2 + 1 || g.K % (B.PH * B.PW) != 0) return false;
+        if ((int64_t)(g.K / (B.PH * B.PW)) * B.H * B.W >= (1ll << 31)) return false;      // (the kernel's table holds 31-bit pixel indices)
+    }
+    if ((cdiv64(g.K, g.splitk) + BK - 1) / BK * BK < WGRAD1_MIN_KCHUNK) return false;
+    // (what koaf_gemm's vector path asks of the pointers; an unaligned call takes the generic kernel's scalar path)
+    if (!aligned16(A.ptr) || !aligned16(B.ptr) || !aligned16(g.C)) return false;
+    if (A.tf && (A.tf != 2 || !A.ptr2 || !A.sc || !A.sh || !A.sc2 || !aligned16(A.ptr2) || !aligned16(A.sc) || !aligned16(A.sh) || !aligned16(A.sc2)))
+        return false;
+    if (B.tf && (B.tf != 1 || !B.sc || !B.sh || !aligned16(B.sc) || !aligned16(B.sh))) return false;
+    if (bm_) { *bm_ = bm; *bn_ = bn; }
+    return true;
+}
+
 // the weight gradient described by g (koaf_conv2d_wgrad's descriptor: A = dy [K][M] K-major with tf 0 | 2, B = x with tf 0 | 1 -- [K][N]
-// K-major for 1x1 / stride 1, or gather 1 over the NHWC tensor for stride 2 --, fmt 1, act16 0, C = slabs or dw) on bm x bn tiles; the
-// caller has checked the dispatch rule (koaf_conv.hip wgrad1_tile)
-int koaf_wgrad1(const KoafGemm& g, int bm, int bn, void* stream) {
+// K-major for 1x1 / stride 1, or gather 1 over the NHWC tensor for stride 2 --, fmt 1, act16 0, C = slabs or dw) on the rule's tile
+int koaf_wgrad1(const KoafGemm& g, void* stream) {
     const KoafOperand& B = g.B;
     const bool gb = B.gather == 1;
-    KOAF_REQUIRE(g.fmt == 1 && g.act16 == 0 && g.A.kind == 1 && B.kind == 1 && !g.A.gather && (B.gather == 0 || gb) && g.A.amax && g.A.ptr && B.ptr &&
-                 g.C && (g.A.tf == 0 || (g.A.tf == 2 && g.A.ptr2 && g.A.sc && g.A.sh && g.A.sc2)) && (B.tf == 0 || (B.tf == 1 && B.sc && B.sh)) &&
-                 (bm == 256 || bm == 128) && (bn == 256 || bn == 128) && bm + bn >= 384 && g.M % bm == 0 && g.N % bn == 0 && g.K >= BK && g.K < (1 << 30) &&
-                 g.splitk >= 1 && g.splitk <= 65535 && g.A.ld == g.M && (gb || B.ld == g.N) && g.ldc == g.N,
-                 "koaf_wgrad1: bad args");
-    // the gathered form: stride 2, a 1x1 / pad 0 or 3x3 / pad 1 filter, the whole pixel is the tap's channels, a column tile inside one tap,
-    // k = whole images of the output grid, and a source pixel index that fits the table's 31 bits
-    KOAF_REQUIRE(!gb || (B.stride == 2 && B.KH == B.KW && B.pad == B.pad_w && ((B.KH == 1 && B.pad == 0) || (B.KH == 3 && B.pad == 1)) &&
-                         (B.CS == 0 || B.CS == B.C) && B.C % bn == 0 && g.N == B.KH * B.KW * B.C && B.PH > 0 && B.PW > 0 &&
-                         B.PH == (B.H + 2 * B.pad - B.KH) / 2 + 1 && B.PW == (B.W + 2 * B.pad_w - B.KW) / 2 + 1 && g.K % (B.PH * B.PW) == 0 &&
-                         (int64_t)(g.K / (B.PH * B.PW)) * B.H * B.W < (1ll << 31)),
-                 "koaf_wgrad1: bad gather");
+    int bm = 0, bn = 0;
+    KOAF_REQUIRE(koaf_wgrad1_ok(g, &bm, &bn), "koaf_wgrad1: bad args");
     Wg1Params p;
     p.a = g.A.ptr; p.a2 = g.A.ptr2; p.asc = g.A.sc; p.ash = g.A.sh; p.asc2 = g.A.sc2; p.a_amax = g.A.amax;
     p.b = B.ptr; p.bsc = B.sc; p.bsh = B.sh;

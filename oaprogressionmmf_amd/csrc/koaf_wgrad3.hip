@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "koaf.h"
 #include "koaf_pieces.h"
+#include "koaf_conv_units.h"
 
 namespace {
 struct Wg3Params {

@@ -4,7 +4,7 @@ koaf_conv2d_dgrad_bnb splits a stride-2 data gradient into the four parity class
 transposed gather over its own taps, and hands every class to koaf_dgrad_s2 when the call runs the fp16 scheme with the weights' D plane
 image on fp32 tensors, without residual, with no fused reduction or BatchNorm-backward mode 2 with one BatchNorm, 3x3 / pad 1 from dy's
 plane images or 1x1 / pad 0 from the fp32 dy (tf 0 | 2), Cout % 32 == 0, Cin % 128 == 0, H and W even and N (H/2) (W/2) a whole number
-of 256-row tiles (koaf_conv.hip dgrad_s2_ok).  Every row of CASES is the smallest shape of its kind; it goes through ops.conv2d_dgrad as
+of 256-row tiles (koaf_dgrad_s2.hip koaf_dgrad_s2_ok).  Every row of CASES is the smallest shape of its kind; it goes through ops.conv2d_dgrad as
 the model calls it, with the outputs pre-filled with NaN, and ASSERTS FROM THE LAUNCH RECORD the variant, the tile and the four records
 (one per class, class order, K = 0 for a class without a tap).
 
@@ -28,11 +28,13 @@ from collections import namedtuple
 import pytest
 import torch
 
+import tile256_refs as R
 from test_tiles_gpu import BWD, Record, _class_rows, _dgrad64, band_errors, componentwise, rel_err
+from tile256_refs import GEN, classes, out_hw
 
 pytestmark = pytest.mark.gpu
 
-DS2, GEN = "koaf_dgrad_s2", "koaf_gemm"
+DS2 = "koaf_dgrad_s2"
 Case = namedtuple("Case", "name shape call bn")
 # shape (N, H, W, Cin, Cout, k, pad), stride 2
 # call: bnb2_amax / bnb2 (BnApply through plane images, fused reduction mode 2, with / without max |dz|) | planes_plain (dy + amax through
@@ -61,30 +63,12 @@ REFUSALS = [
 ]
 
 
-def out_hw(shape, stride=2):
-    N, H, W, Cin, Cout, k, pad = shape
-    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-
-
-def classes(shape):
-    """(py, px, Hc, Wc, khs, kws, nkh, nkw, offy, offx) of the four parity classes, as koaf_conv2d_dgrad_bnb forms them"""
-    N, H, W, Cin, Cout, k, pad = shape
-    out = []
-    for py in range(2):
-        for px in range(2):
-            khs, kws = (py + pad) & 1, (px + pad) & 1
-            nkh, nkw = ((k - khs + 1) // 2 if khs < k else 0), ((k - kws + 1) // 2 if kws < k else 0)
-            out.append((py, px, (H - py + 1) // 2, (W - px + 1) // 2, khs, kws, nkh, nkw, (py + pad - khs) // 2, (px + pad - kws) // 2))
-    return out
-
-
 def inputs(shape, dev, stride=2, bf16=False):
     """device operands of a shape: the packed weight with its plane images, a plain dy with its amax, a BnApply of the same size, the
     producer's conv output cx with its BatchNorm record sv (mode 2 masks by the sign of sc * cx + sh: kept out of rounding's reach)"""
     from oaprogressionmmf_amd import ops
     N, H, W, Cin, Cout, k, pad = shape
     OH, OW = out_hw(shape, stride)
-    orow = N * OH * OW
     g_ = torch.Generator(device=dev).manual_seed(9900 + sum(shape))
 
     def rnd(*s):
@@ -92,13 +76,8 @@ def inputs(shape, dev, stride=2, bf16=False):
     t = dict(w=rnd(Cout, k, k, Cin) * (k * k * Cin) ** -0.5, dy=rnd(N, OH, OW, Cout) * 1e-3)
     t["am"] = t["dy"].abs().max().reshape(1).float()
     t["img"] = ops.build_weight_planes(t["w"], Cout, k * k, Cin)
-    c = rnd(N, OH, OW, Cout) * 1.5 + 0.3
-    c = c.bfloat16() if bf16 else c
-    gam, bet = rnd(Cout) * 0.2 + 1, rnd(Cout) * 0.1
-    svc = ops.bn_finalize(ops.colstats(c, orow, Cout), Cout, orow, gam, bet, torch.zeros(Cout, device=dev), torch.ones(Cout, device=dev),
-                          torch.zeros(1, dtype=torch.int64, device=dev), 0.1, 1e-5, True)
-    dgm, dbt = torch.empty(Cout, device=dev), torch.empty(Cout, device=dev)
-    t["apply"] = ops.bn_bwd(rnd(N, OH, OW, Cout) * 1e-3, c, svc, orow, Cout, orow, dgm, dbt, 2, fused=True)
+    t["apply"] = R.bn_apply(dev, N * OH * OW, Cout, c=rnd(N, OH, OW, Cout) * 1.5 + 0.3, gam=rnd(Cout) * 0.2 + 1, bet=rnd(Cout) * 0.1,
+                            dz=rnd(N, OH, OW, Cout) * 1e-3, store16=bf16)
     sv = torch.stack([rnd(Cin) * 0.3, torch.rand(Cin, generator=g_, device=dev) + 0.5, (rnd(Cin) * 0.5 + 1).abs().clamp(min=0.25), rnd(Cin) * 0.2])
     cx = rnd(N, H, W, Cin) * 1.5 + 0.3
     cx = torch.where((cx * sv[2] + sv[3]).abs() < 1e-3, cx + 0.1, cx)
@@ -114,23 +93,14 @@ def call_model(shape, t, call, stride=2, **kw):
     """ops.conv2d_dgrad as the model calls it, every output pre-filled with NaN -> (the outputs as a tuple, the launch records)"""
     from oaprogressionmmf_amd import ops
     N, H, W, Cin, Cout, k, pad = shape
-    real_empty = ops.conv._empty
-
-    def nan_empty(*a, **k_):
-        out = real_empty(*a, **k_)
-        return out.fill_(float("nan")) if out.is_floating_point() else out
     use_apply = call in ("bnb2_amax", "bnb2", "apply")
     kw.setdefault("wimg", t["img"])
     if not use_apply:
         kw.setdefault("dy_amax", t["am"])
     if call.startswith("bnb2"):
         kw["bnb"] = dict(mode=2, c=t["cx"], saved=t["sv"], dz_amax=call == "bnb2_amax")
-    ops.conv._empty = nan_empty
-    try:
-        with Record() as rec:
-            out = ops.conv2d_dgrad(t["apply"] if use_apply else t["dy"], t["w"], N, H, W, Cin, Cout, k, k, stride, pad, **kw)
-    finally:
-        ops.conv._empty = real_empty
+    with R.nan_outputs(), Record() as rec:
+        out = ops.conv2d_dgrad(t["apply"] if use_apply else t["dy"], t["w"], N, H, W, Cin, Cout, k, k, stride, pad, **kw)
     torch.cuda.synchronize()
     return (out if isinstance(out, tuple) else (out,)), rec.launches
 
@@ -138,49 +108,19 @@ def call_model(shape, t, call, stride=2, **kw):
 def call_generic(dev, shape, t, call):
     """the generic path: koaf_gemm on the four class descriptors koaf_conv2d_dgrad_bnb builds, 128 x 128 tiles pinned, the partial rows
     class after class -> ((dx, part, amax) as far as the call has them, the launch records)"""
-    from oaprogressionmmf_amd import _lib, ops
+    from oaprogressionmmf_amd import ops
     N, H, W, Cin, Cout, k, pad = shape
     OH, OW = out_hw(shape)
-    npo = N * OH * OW
     use_apply, bnb = call in ("bnb2_amax", "bnb2", "apply"), call.startswith("bnb2")
-    f, d, wamax = t["img"]
-    ap = t["apply"]
     planes = None
     if k == 3:
-        planes = ops.conv._dy_planes(ap if use_apply else t["dy"], None if use_apply else t["am"], npo, Cout)
+        planes = ops.conv._dy_planes(t["apply"] if use_apply else t["dy"], None if use_apply else t["am"], N * OH * OW, Cout)
     dx = torch.full((N, H, W, Cin), float("nan"), device=dev)
     nrows = sum(N * c[2] * c[3] // 128 for c in classes(shape))
     part = torch.full((nrows, 2, Cin), float("nan"), device=dev) if bnb else None
     amax = torch.zeros(1, device=dev) if call == "bnb2_amax" else None
-    rows_done = 0
     with Record() as rec:
-        for py, px, Hc, Wc, khs, kws, nkh, nkw, offy, offx in classes(shape):
-            g = _lib.KoafGemm()
-            g.alpha, g.nb0, g.nb1, g.splitk, g.fmt, g.prec = 1.0, 1, 1, 1, 1, 1
-            g.A.amax, g.B.amax = (ap.amax if use_apply else t["am"]).data_ptr(), wamax.data_ptr()
-            g.A.kind, g.A.gather = 0, 2
-            if use_apply:
-                g.A.ptr, g.A.ptr2, g.A.tf = ap.dz.data_ptr(), ap.c.data_ptr(), 2
-                g.A.sc, g.A.sc2, g.A.sh = ap.coef.data_ptr(), ap.coef.data_ptr() + 8 * Cout, ap.coef.data_ptr() + 12 * Cout
-            else:
-                g.A.ptr = t["dy"].data_ptr()
-            g.A.H, g.A.W, g.A.C, g.A.CS, g.A.PH, g.A.PW = OH, OW, Cout, Cout, Hc, Wc
-            g.A.KH, g.A.KW, g.A.stride, g.A.pad, g.A.pad_w = max(nkh, 1), max(nkw, 1), 1, offy, offx
-            g.B.ptr, g.B.kind, g.B.gather, g.B.C, g.B.KW = t["w"].data_ptr() + 4 * (khs * k + kws) * Cin, 2, 0, Cout, g.A.KW
-            g.B.planes, g.B.ld, g.B.plane_stride = d.data_ptr() + 2 * (khs * k + kws) * Cout, k * k * Cout, Cin * k * k * Cout
-            g.B.tap_stride, g.B.tap_stride_h = 2 * Cout, 2 * k * Cout
-            if planes is not None and nkh > 0 and nkw > 0:
-                g.A.kind, g.A.planes, g.A.plane_stride, g.A.zeros = 2, planes.data_ptr(), npo * Cout, planes.data_ptr() + 4 * npo * Cout
-                g.A.ptr, g.A.ptr2, g.A.tf, g.A.sc, g.A.sh, g.A.sc2 = None, None, 0, None, None, None
-            g.M, g.N, g.K, g.bm, g.bn = N * Hc * Wc, Cin, nkh * nkw * Cout, 128, 128
-            g.C, g.ldc, g.ldr = dx.data_ptr(), Cin, Cin
-            g.cmap, g.cm_PH, g.cm_PW, g.cm_H, g.cm_W, g.cm_py, g.cm_px = 1, Hc, Wc, H, W, py, px
-            if bnb:
-                sv = t["sv"]
-                g.bnb_mode, g.bnb_c, g.bnb_amax = 2, t["cx"].data_ptr(), amax.data_ptr() if amax is not None else None
-                g.bnb_mean, g.bnb_invstd, g.bnb_sc, g.bnb_sh = sv[0].data_ptr(), sv[1].data_ptr(), sv[2].data_ptr(), sv[3].data_ptr()
-                g.bnb_part = part.data_ptr() + 4 * rows_done * 2 * Cin
-                rows_done += g.M // 128
+        for g in R.dgrad_class_descriptors(shape, t, call, dx, part, amax, planes):
             ops.gemm(g)
     torch.cuda.synchronize()
     return (dx,) + ((part,) if bnb else ()) + ((amax,) if amax is not None else ()), rec.launches
@@ -232,15 +172,14 @@ def test_256_row_kernel_equals_the_generic_path(dev, case):
     try:
         t = inputs(case.shape, dev)
         out, launches = call_model(case.shape, t, case.call)
-        gemms = [r for r in launches if r["variant"] in (DS2, GEN) or r["variant"].startswith(GEN)]
+        gemms = R.records(launches)
         assert len(gemms) == 4, (case.name, launches)
         a_tf = 2 if case.call == "apply" else 0
         for r, c in zip(gemms, cls):
             M, K = N * c[2] * c[3], c[6] * c[7] * Cout
             tiles = (M // 256) * (Cin // case.bn)
-            want = dict(variant=DS2, bm=256, bn=case.bn, tiles=tiles, grid_x=tiles, splitk=1, nbatch=1, M=M, N=Cin, K=K, fmt=1, a_tf=a_tf,
-                        b_tf=0, act16=0, emit=0)
-            assert {f: r[f] for f in want} == want, (case.name, r, want)
+            R.hold_record(case.name, r, dict(variant=DS2, bm=256, bn=case.bn, tiles=tiles, grid_x=tiles, splitk=1, nbatch=1, M=M, N=Cin, K=K, fmt=1,
+                                             a_tf=a_tf, b_tf=0, act16=0, emit=0))
         assert [r["K"] > 0 for r in gemms] == ([True] * 4 if k == 3 else [True, False, False, False]), (case.name, gemms)
         for o in out:
             assert bool(torch.isfinite(o).all()), (case.name, "an output element was not written")
@@ -265,7 +204,6 @@ def test_256_row_kernel_equals_the_generic_path(dev, case):
 
 @pytest.mark.parametrize("case", REFUSALS, ids=[c.name for c in REFUSALS])
 def test_refused_calls_stay_on_the_generic_kernel(dev, case):
-    N, H, W, Cin, Cout, k, pad = case.shape
     try:
         t = inputs(case.shape, dev, case.stride, bf16=case.how == "bf16")
         kw, call = {}, "planes_plain"
@@ -280,11 +218,6 @@ def test_refused_calls_stay_on_the_generic_kernel(dev, case):
         if case.how == "noplanes":
             kw["aplanes"] = False
         out, launches = call_model(case.shape, t, call, stride=case.stride, **kw)
-        gemms = [r for r in launches if r["variant"].startswith("koaf_")]
-        assert gemms and all(r["variant"] != DS2 for r in launches), (case.name, launches)
-        assert all(r["variant"] == GEN for r in gemms if r["K"] > 0), (case.name, launches)
-        assert all(r["fmt"] == (0 if case.how == "noimg" else 1) and r["act16"] == (2 if case.how == "bf16" else 0) for r in gemms), (case.name, gemms)
-        for o in out:
-            assert bool(torch.isfinite(o.float()).all()), case.name
+        R.hold_refusal(case.name, launches, DS2, out, 0 if case.how == "noimg" else 1, 2 if case.how == "bf16" else 0, every=True)
     finally:
         torch.cuda.empty_cache()
