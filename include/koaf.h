@@ -940,6 +940,60 @@ int koaf_range_metrics(const int32_t* packed, int32_t n, const int32_t* idx, int
 int koaf_confusion(const int32_t* y_true, const int32_t* y_pred, int64_t n, int32_t K, int64_t* counts, uint32_t* flag,
                    void* stream);
 
+/* ---- calibration of the predicted probabilities (koaf_calib.hip; scikit-learn's brier_score_loss, log_loss and
+ * calibration_curve, numpy's percentile, and the usual companions of a clinical prediction model: ECE / MCE, calibration
+ * intercept and slope, temperature scaling, net benefit): for the sample itself and for R bootstrap resamples, one block of 256
+ * threads per row; rows, idx, m and with_identity as for koaf_curve_metrics (m <= KOAF_METRICS_MAX_N).  scores are fp32, or fp64
+ * when f64, read in place as scores[i * stride] and widened to fp64 (exact); labels is int32 [n] of 0 / 1.
+ * Arithmetic contract: everything is fp64; counts are INTEGER (LDS integer atomics, per-thread counters); every fp64 sum has one
+ * owner and a fixed order -- thread t adds the draws [t L, (t + 1) L) of its row, L = ceil(draws / 256), in row order, then a
+ * fixed tree runs over the 256 threads -- without fused multiply-add.  No floating-point atomics: the same bits from run to run.
+ * Every loop bound is a constant or an argument.  `draws` below is the row's length: n for the identity row, m otherwise.
+ * flag: bits 0-2 as for koaf_score_ranks / koaf_curve_metrics (a NaN / Inf score; a label other than 0 / 1, which counts as 0;
+ * an index outside [0, n), which is skipped and never followed); bit 3: a row of koaf_recalib_fit ended with a status other than 0.
+ *
+ * koaf_calib_edges  one block.  edges[k] = np.percentile(scores, 100 q[k]) (default linear method) for the nbins + 1 fractions q
+ *   (device fp64, in [0, 1]; the quantile strategy of calibration_curve passes np.linspace(0, 1, nbins + 1)): virtual index
+ *   h = q * (n - 1), lo = floor(h), the order statistics a = x_(lo), b = x_(min(lo + 1, n - 1)) found by all-pairs counting (no
+ *   sort: element i is x_(k) for every k with #{s < s_i} <= k < #{s <= s_i}), t = h - lo, and numpy's two-sided lerp
+ *   a + (b - a) * t, replaced by b - (b - a) * (1 - t) where t >= 0.5; h >= n - 1 gives the largest score.  Bit-equal to numpy
+ *   on fp64 scores; fp32 scores are widened first (numpy would interpolate in fp32).
+ * koaf_calib_metrics  edges is device fp64 [nbins + 1] (only the inner edges are read), thr device fp64 [T] (nullable with
+ *   T = 0; each in (0, 1), any order), 1 <= nbins <= KOAF_CALIB_MAX_BINS, 0 <= T <= KOAF_CALIB_MAX_THR.  The bin of p is
+ *   #{ k in 1 .. nbins - 1 : edges[k] < p } compared in fp64 -- np.searchsorted(edges[1:-1], p, side="left"): a score on an edge
+ *   goes to the lower bin.  With y the label, n_b / S_y,b / S_p,b the count, the positives and the score sum of bin b:
+ *     out[r] = { P, N,  sum (p - y)^2 / draws,  sum -log(clip(p_y, eps, 1 - eps)) / draws,  sum p / draws,
+ *                (sum_b |S_y,b - S_p,b|) / draws  (b ascending),  max over non-empty b of |S_y,b - S_p,b| / n_b,  bins in use }
+ *   p_y = p for y = 1 and 1 - p otherwise.  A one-class row keeps every value (they are defined there); only P or N is 0.
+ *   bins [rows][nbins][3] (nullable) = (n_b, S_y,b, S_p,b), the two counts held as fp64.
+ *   nb [rows][T][4] (nullable) = (tp, fp, tp / draws - (fp / draws) * (t / (1 - t)), P / draws - (N / draws) * (t / (1 - t))) of
+ *   the prediction p >= t: the net benefit of the model and, from the same expression at tp = P, fp = N, of treating everyone.
+ * koaf_recalib_fit  unpenalised logistic regression of y on eta = a + b x, one block per row.  kind 0: x = log(q) - log1p(-q),
+ *   q = clip(p, eps, 1 - eps), the scores being probabilities; kind 1: x = the score, minus scores0[i * stride0] when scores0 (same
+ *   dtype; the logit difference of a (B, 2) logits tensor read in place) is given.  mode 0: a and b free (calibration intercept and
+ *   slope); mode 1: b only, a = 0 (temperature scaling of two classes, T = 1 / b); mode 2: a only, b = 1 (calibration in the
+ *   large).  From (0, 1), Newton steps on L = sum softplus(eta) - y eta with the Hessian from sigma (1 - sigma), solved in closed
+ *   form; the step is halved, at most 30 times, until L does not increase (beyond 2^-45 |L|, the rounding of the sum itself: near
+ *   the optimum a Newton step changes L by less); it stops when max|g_free| / draws <= tol (status 0),
+ *   after max_iter <= KOAF_RECALIB_MAX_ITER steps or when no halved step keeps L from increasing (status 1), when the Hessian is
+ *   not positive, a value leaves the finite range or -- modes 0 and 1 -- the current line puts every draw strictly on its class's
+ *   side (complete separation: L has no finite minimum) (status 2), or at once when the row holds one class (status 3).
+ *     report[r] = { a, b, steps taken, max|g_free| / draws, L / draws, status, P, N };  a and b are NaN for status >= 2.
+ * koaf_recalib_apply  out[i] = sigma(a + b x_i) (fp64 [n], n < 2^31), x as in the fit; element-wise. */
+#define KOAF_CALIB_MAX_BINS 64
+#define KOAF_CALIB_MAX_THR 128
+#define KOAF_RECALIB_MAX_ITER 200
+int koaf_calib_edges(const void* scores, int32_t f64, int64_t stride, int32_t n, const double* q, int32_t nbins, double* edges,
+                     uint32_t* flag, void* stream);
+int koaf_calib_metrics(const void* scores, int32_t f64, int64_t stride, const int32_t* labels, int32_t n, const double* edges,
+                       int32_t nbins, const double* thr, int32_t T, const int32_t* idx, int32_t R, int32_t m, int32_t with_identity,
+                       double eps, double* out, double* bins, double* nb, uint32_t* flag, void* stream);
+int koaf_recalib_fit(const void* scores, int32_t f64, int64_t stride, const void* scores0, int64_t stride0, const int32_t* labels,
+                     int32_t n, int32_t kind, int32_t mode, const int32_t* idx, int32_t R, int32_t m, int32_t with_identity,
+                     double eps, double tol, int32_t max_iter, double* report, uint32_t* flag, void* stream);
+int koaf_recalib_apply(const void* scores, int32_t f64, int64_t stride, const void* scores0, int64_t stride0, int64_t n, int32_t kind,
+                       double a, double b, double eps, double* out, uint32_t* flag, void* stream);
+
 /* ---- the clinical logistic-regression baseline (koaf_clin.hip; run/train_prog_clin.py with scikit-learn's StandardScaler,
  * OneHotEncoder and LogisticRegression(lbfgs, L2, fit_intercept) behind it).  Everything is fp64.  Every sum has one owner and a
  * fixed order and there are no floating-point atomics: the same bits from run to run.  *flag is a device word the caller zeroed;

@@ -13,11 +13,13 @@ Callers use `ops.<name>`: everything is re-exported here, and this package and `
 PROFILE = None
 
 from .._lib import KoafBnApply, KoafBnb, KoafEmit, KoafError, KoafGemm, KoafLaunchRec, KoafTail, KoafWImg, KoafWPlane, check, defines, lib
-from . import _base, bn, clin, conv, dense, explain, inputs, metrics, mriprep, train
+from . import _base, bn, calib, clin, conv, dense, explain, inputs, metrics, mriprep, train
 from ._base import (_STATUS_BY_DEV, _a16, _empty, _i32, _prof_begin, _prof_end, _ptr, _status_buffer, _stream, check_numerics, conv_out,
                     numerics_status)
 from .bn import (BnApply, _bn_bwd_tail, _colpart_rows, _dy_args, _reduce_ws, bn_add_relu, bn_bwd, bn_bwd_from_part, bn_finalize, colstats,
                  gap_bwd, gap_fwd, maxpool_bwd, maxpool_fwd)
+from .calib import (CALIB_EPS, CALIB_FLAG_TEXT, CALIB_MAX_BINS, CALIB_MAX_THR, RECALIB_KINDS, RECALIB_MAX_ITER, RECALIB_MODES,
+                    RECALIB_STATUS, calib_edges, calib_flag, calib_metrics, calib_raise, recalib_apply, recalib_fit)
 from .clin import CLIN_FLAG_TEXT, LOGREG_MAX_P, clin_design, clin_flag, clin_raise, logreg_fit, logreg_predict
 from .conv import (ACT_SCALE, CONV_F16, _dy_planes, _img, _rup, _slab_ws, act_planes, build_weight_planes, conv2d_dgrad, conv2d_fwd,
                    conv2d_wgrad, gconv3x3_dgrad, gconv3x3_fwd, gconv3x3_wgrad, gconv_compress_dw, gconv_expand_w, gemm, launch_log,

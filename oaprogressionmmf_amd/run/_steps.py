@@ -79,13 +79,15 @@ def predict_batch(model, xs, downscale=None):
     return logits, proba
 
 
-def val_epoch(model, loss_fn, batches, downscale=None, *, target, kws_metrics=None):
+def val_epoch(model, loss_fn, batches, downscale=None, *, target, kws_metrics=None, calibration=None):
     """`ProgressionPrediction.val_epoch` (train_prog_fus.py:172-236) over an iterable of (xs, ys) device batches; the model must
     already be in eval() mode.  Per batch one forward (predict_batch) and the loss of its logits, all under no_grad; the
     probabilities and targets stay on the device and go to various.calc_metrics_v2 as device tensors, the losses are read back
     once at the end and the numerics status words are looked at once per pass: no per-batch host sync.
     target: config.data.target (calc_metrics_v2 refuses names it does not know); kws_metrics: further keyword arguments of
-    calc_metrics_v2 (bootstrap, kws_ppv, kws_bs).
+    calc_metrics_v2 (bootstrap, kws_ppv, kws_bs).  calibration: None, or a dict of keyword arguments of various.calc_calibration
+    (n_bins, strategy, thresholds, bootstrap, kws_bs; {} for its defaults) -- epoch-w then gains a "calibration" entry, the
+    calibration table of the same device tensors.
     Returns the reference's dict: {"batch-w": {"loss_prog": [np.round(loss, 3), ...]}, "epoch-w": calc_metrics_v2(...)} --
     fit() reads its checkpoint criterion from it (the mean of loss_prog, or epoch-w's b_accuracy / avg_precision)."""
     from ..various._metrics import calc_metrics_v2
@@ -99,7 +101,11 @@ def val_epoch(model, loss_fn, batches, downscale=None, *, target, kws_metrics=No
         if not losses:
             raise ValueError("val_epoch: no batches")
         loss_host = torch.stack(losses).cpu()
-        epoch_w = calc_metrics_v2(prog_target=torch.cat(targets), prog_pred_proba=torch.cat(probas, dim=0), target=target,
-                                  **(kws_metrics or {}))
+        prog_target, prog_pred_proba = torch.cat(targets), torch.cat(probas, dim=0)
+        epoch_w = calc_metrics_v2(prog_target=prog_target, prog_pred_proba=prog_pred_proba, target=target, **(kws_metrics or {}))
+        if calibration is not None:
+            from ..various._calibration import calc_calibration
+            epoch_w["calibration"] = calc_calibration(prog_target=prog_target, prog_pred_proba=prog_pred_proba, target=target,
+                                                      **dict(calibration))
     ops.check_numerics()
     return {"batch-w": {"loss_prog": [np.round(float(v), 3) for v in loss_host]}, "epoch-w": epoch_w}

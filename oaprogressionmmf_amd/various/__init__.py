@@ -1,4 +1,6 @@
 """Mirror of koafusion/various/__init__.py:1-11 for the hot-path pieces."""
+from ._calibration import (Recalibrator, brier_score_loss, calc_calibration, calibration_curve, calibration_slope_intercept,
+                           decision_curve, expected_calibration_error, fit_temperature, log_loss)
 from ._checkpoint import CheckpointHandler, load_train_state, save_train_state
 from ._clip import clip_grad_norm_
 from ._losses import dict_losses
