@@ -16,6 +16,56 @@ namespace {
 // per-element values itself (koafusion/various/_losses.py:101-108: reduction 'none', then .mean()), still divides by every
 // element, as the reference does.  Any other out-of-range label (torch raises a device assert there) is treated the same way
 // and counted in the numerics status word [1] instead of indexing out of bounds.
+//
+// One element i of [B][S], shared by the one-block and the grid form: writes its gradient column d[j * S] (times wgt, the
+// reduction's factor) and returns its loss.  The softmax losses do not depend on a common offset of the logits, and neither
+// does this arithmetic: the row maximum m is subtracted before anything is added to it (lse = m + log s would round every
+// log-probability to ulp(m)).  With jm the first class at the maximum and s1 the sum of the OTHER classes' exp(x - m),
+//   log p_j = (x_j - m) - log1p(s1),   1 - p = -expm1(log p),
+// so that a confident row keeps the relative accuracy of its small quantities (1 - pt, the target's gradient) where 1 - exp()
+// and log(1 + tiny) would cancel.
+__device__ __forceinline__ float loss_one(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                          const float* __restrict__ cw, float* __restrict__ dlogits, int64_t i, int C, int64_t S,
+                                          float gamma, int focal, float wgt, unsigned& nbad) {
+    const int64_t b = i / S, sp = i - b * S;
+    const float* x = logits + b * C * S + sp;        // class j at x[j * S]
+    float* d = dlogits + b * C * S + sp;
+    const int64_t tg64 = target[i];
+    if (tg64 < 0 || tg64 >= C) {
+        nbad += (tg64 != -100) ? 1u : 0u;
+        for (int j = 0; j < C; ++j) d[j * S] = 0.f;
+        return 0.f;
+    }
+    float m = x[0];
+    int jm = 0;
+    for (int j = 1; j < C; ++j) {
+        const float v = x[j * S];
+        if (v > m) { m = v; jm = j; }
+    }
+    float s1 = 0.f;
+    for (int j = 0; j < C; ++j)
+        if (j != jm) s1 += expf(x[j * S] - m);
+    const float ls = log1pf(s1);
+    const int tg = (int)tg64;
+    const float w = cw ? cw[tg] : 1.f;
+    const float lp = (x[tg * S] - m) - ls;           // log_softmax(x)[tg]
+    const float logpt = w * lp;
+    float li, dl;  // loss_i, d loss_i / d logpt
+    if (focal) {
+        const float pt = expf(logpt), om = -expm1f(logpt);
+        const float pw = powf(om, gamma);
+        li = -pw * logpt;
+        const float pw1 = (gamma == 0.f) ? 0.f : gamma * powf(om, gamma - 1.f);
+        dl = -pw + pw1 * pt * logpt;
+    } else {
+        li = -logpt;
+        dl = -1.f;
+    }
+    const float c = dl * w * wgt, omp = -expm1f(lp);  // omp = 1 - softmax(x)[tg]
+    for (int j = 0; j < C; ++j) d[j * S] = c * (j == tg ? omp : -expf((x[j * S] - m) - ls));
+    return li;
+}
+
 __global__ void __launch_bounds__(256) focal_loss_kernel(const float* __restrict__ logits,
                                                          const int64_t* __restrict__ target, const float* __restrict__ cw,
                                                          float* loss, float* __restrict__ dlogits, int B, int C, int64_t S,
@@ -41,42 +91,7 @@ __global__ void __launch_bounds__(256) focal_loss_kernel(const float* __restrict
     }
     float acc = 0.f;
     const float wgt = mean ? 1.f / wsum : 1.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) {
-        const int64_t b = i / S, sp = i - b * S;
-        const float* x = logits + b * C * S + sp;        // class j at x[j * S]
-        float* d = dlogits + b * C * S + sp;
-        const int64_t tg64 = target[i];
-        if (tg64 < 0 || tg64 >= C) {
-            nbad += (tg64 != -100) ? 1u : 0u;
-            for (int j = 0; j < C; ++j) d[j * S] = 0.f;
-            continue;
-        }
-        float m = -INFINITY;
-        for (int j = 0; j < C; ++j) m = fmaxf(m, x[j * S]);
-        float s = 0.f;
-        for (int j = 0; j < C; ++j) s += expf(x[j * S] - m);
-        const float lse = m + logf(s);
-        const int tg = (int)tg64;
-        const float w = cw ? cw[tg] : 1.f;
-        const float logpt = w * (x[tg * S] - lse);
-        const float pt = expf(logpt);
-        float li, dl;  // loss_i, d loss_i / d logpt
-        if (focal) {
-            const float om = 1.f - pt;
-            const float pw = powf(om, gamma);
-            li = -pw * logpt;
-            const float pw1 = (gamma == 0.f) ? 0.f : gamma * powf(om, gamma - 1.f);
-            dl = -pw + pw1 * pt * logpt;
-        } else {
-            li = -logpt;
-            dl = -1.f;
-        }
-        acc += li;
-        for (int j = 0; j < C; ++j) {
-            const float pj = expf(x[j * S] - lse);
-            d[j * S] = dl * w * ((j == tg ? 1.f : 0.f) - pj) * wgt;
-        }
-    }
+    for (int64_t i = threadIdx.x; i < n; i += 256) acc += loss_one(logits, target, cw, dlogits, i, C, S, gamma, focal, wgt, nbad);
     koaf_status_add(status, 1, nbad);
     red[threadIdx.x] = acc;
     __syncthreads();
@@ -109,42 +124,7 @@ __global__ void __launch_bounds__(256) loss_grid_kernel(const float* __restrict_
         }
     } else {
         const float wgt = mean ? 1.f / (wden ? *wden : (float)n) : 1.f;
-        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
-            const int64_t b = i / S, sp = i - b * S;
-            const float* x = logits + b * C * S + sp;
-            float* d = dlogits + b * C * S + sp;
-            const int64_t tg64 = target[i];
-            if (tg64 < 0 || tg64 >= C) {
-                nbad += (tg64 != -100) ? 1u : 0u;
-                for (int j = 0; j < C; ++j) d[j * S] = 0.f;
-                continue;
-            }
-            float m = -INFINITY;
-            for (int j = 0; j < C; ++j) m = fmaxf(m, x[j * S]);
-            float se = 0.f;
-            for (int j = 0; j < C; ++j) se += expf(x[j * S] - m);
-            const float lse = m + logf(se);
-            const int tg = (int)tg64;
-            const float w = cw ? cw[tg] : 1.f;
-            const float logpt = w * (x[tg * S] - lse);
-            const float pt = expf(logpt);
-            float li, dl;
-            if (focal) {
-                const float om = 1.f - pt;
-                const float pw = powf(om, gamma);
-                li = -pw * logpt;
-                const float pw1 = (gamma == 0.f) ? 0.f : gamma * powf(om, gamma - 1.f);
-                dl = -pw + pw1 * pt * logpt;
-            } else {
-                li = -logpt;
-                dl = -1.f;
-            }
-            acc += li;
-            for (int j = 0; j < C; ++j) {
-                const float pj = expf(x[j * S] - lse);
-                d[j * S] = dl * w * ((j == tg ? 1.f : 0.f) - pj) * wgt;
-            }
-        }
+        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) acc += loss_one(logits, target, cw, dlogits, i, C, S, gamma, focal, wgt, nbad);
         koaf_status_add(status, 1, nbad);
     }
     red[threadIdx.x] = acc;

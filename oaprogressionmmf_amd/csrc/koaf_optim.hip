@@ -147,6 +147,10 @@ __global__ void adam_hyper_kernel(int32_t* step, const float* lr, double b1, dou
     hyper[2] = (float)sqrt(bc2);
 }
 
+// torch.maximum: the larger one, and a NaN on either side stays (fmaxf would drop it, and amsgrad's maximum would come out finite
+// beside a NaN second moment)
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                    float omb1, float b2, float omb2, float eps, float wd, float step_size,
@@ -169,7 +173,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
             const float mj = mv[j] + (gj - mv[j]) * omb1;
             const float vj = vv[j] * b2 + omb2 * gj * gj;
             float vd = vj;
-            if (vmax) { vd = fmaxf(xv[j], vj); xv[j] = vd; }     // amsgrad: the running maximum of the second moment
+            if (vmax) { vd = max_nan(xv[j], vj); xv[j] = vd; }   // amsgrad: the running maximum of the second moment
             const float denom = sqrtf(vd) / bc2_sqrt + eps;
             pv[j] = pj - step_size * (mj / denom);
             mv[j] = mj;
@@ -188,7 +192,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
         const float mj = m[i] + (gj - m[i]) * omb1;
         const float vj = v[i] * b2 + omb2 * gj * gj;
         float vd = vj;
-        if (vmax) { vd = fmaxf(vmax[i], vj); vmax[i] = vd; }
+        if (vmax) { vd = max_nan(vmax[i], vj); vmax[i] = vd; }
         p[i] = pj - step_size * (mj / (sqrtf(vd) / bc2_sqrt + eps));
         m[i] = mj;
         v[i] = vj;
